@@ -16,9 +16,11 @@ The step-invariant conditioning is RECOMPUTED every step like the reference does
 Multi-GPU: one process per GPU, each rank denoises its own scene (the 6-view x scene batch shards
 over ranks with no data-path collective) -> weak scaling; `value` = steps of all ranks / time.
 
-Rank 0 prints ONE JSON line (contract in the task statement) incl. `roofline` (dominant kernel by
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run measures the headline only: set-up,
+warm-up, the timed steps, the line.  --full adds the other legs, among them `roofline` (dominant kernel by
 total time, timed live with HIP events on the launch stream during an instrumented eager step)
 and `cpu_baseline` (the CPU oracle timed on the host cores on a bounded sample).
+--dump-outputs DIR writes the latents of the last timed step as DIR/latents.npy (float32).
 """
 import argparse
 import json
@@ -444,8 +446,9 @@ def _roofline_row(name, d, table):
                           "frac_of_guide_lower_bound": round(d["staged"] / d["count"] / avg_s / 1e9 / GUIDE_L2_STAGE_GBPS, 4)})}
 
 
-def measure(args, dtype_name, device, dist, world, rank, backend, want_roofline):
-    """Builds the models in `dtype_name`, captures the step, times args.steps steps; returns a dict."""
+def measure(args, dtype_name, device, dist, world, rank, backend, want_roofline, want_outputs=False):
+    """Builds the models in `dtype_name`, captures the step, times args.steps steps; returns a dict.  want_outputs: the
+    dict also holds `outputs`, what the last timed step handed its caller (the latents), as host float32 tensors."""
     from dualdiff_amd import ops as O
     from dualdiff_amd.pipeline.pipeline_bev_controlnet import BEVDenoiser
     dtype = torch.bfloat16 if dtype_name == "bf16" else torch.float16
@@ -565,6 +568,8 @@ def measure(args, dtype_name, device, dist, world, rank, backend, want_roofline)
         from dualdiff_amd.parallel import max_over_ranks
         elapsed = max_over_ranks(elapsed, device if backend == "nccl" else None)   # slowest rank sets the job's wall time
         finite = bool(torch.isfinite(den.latents.float()).all().item())
+        # taken before the roofline leg: its instrumented eager steps advance the latents further
+        outputs = {"latents": den.latents.float().cpu()} if want_outputs else None
         if not finite and rank == 0:
             print("[bench] WARNING: non-finite latents after the timed steps (%s) — NaN data runs ~5 %% faster than real "
                   "data; this measurement is INVALID" % dtype_name, file=sys.stderr)
@@ -621,7 +626,7 @@ def measure(args, dtype_name, device, dist, world, rank, backend, want_roofline)
     if graph and args.parallelism == "view-split":
         graph = "segments" if kw.get("segmented_graph") else "single"
     return {"elapsed": elapsed, "finite": finite, "roofline": roofline, "graph": graph, "pairs": pairs,
-            "shard": shard_desc, "shard_msg": shard_msg}
+            "shard": shard_desc, "shard_msg": shard_msg, "outputs": outputs}
 
 
 def _short_kernel(name):
@@ -742,6 +747,26 @@ def _write_full_report(full, tag):
         except OSError:
             continue
     return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs DIR: every array of `outputs` as DIR/<name>.npy in float32, at most DUMP_LIMIT_BYTES in all.  An
+    array over its share of the budget is replaced by a fixed seeded sample of its elements, DIR/<name>_sample.npy (the
+    same indices in every run with the same arguments)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // 4 // max(1, len(outputs))           # float32 elements per array
+    for name, t in outputs.items():
+        flat = t.detach().reshape(-1).float().cpu()
+        if flat.numel() > share:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+            arr, name = flat[idx].numpy(), name + "_sample"
+        else:
+            arr = flat.reshape(t.shape).numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 _TORCHRUN_ENV = ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "GROUP_WORLD_SIZE", "ROLE_RANK",
@@ -885,7 +910,8 @@ def _plumbing_check(args, world, rank):
     """Launcher / rendezvous check WITHOUT the measured path (runs on a CPU-only host: tests/test_distributed_cpu.py):
     every rank joins a gloo group, passes the barrier the timed region uses and takes the max-over-ranks of a fake
     elapsed time; rank 0 prints a line with `n_gpus` = the world size and NO value — never a measurement.  With N > 1 in
-    the default mode the strong-scaling leg is orchestrated exactly as in a real run (child job, timeout, one line)."""
+    the default mode and --full the strong-scaling leg is orchestrated exactly as in a real run (child job, timeout, one
+    line)."""
     import torch.distributed as dist
     from dualdiff_amd.parallel import max_over_ranks
     collective = None
@@ -905,7 +931,7 @@ def _plumbing_check(args, world, rank):
            "parallelism": args.parallelism, "env": dd_env()}
     if collective is not None:
         out["collective"] = collective
-    if world > 1 and args.parallelism == "scenes" and args.strong_leg == "auto":
+    if args.full and world > 1 and args.parallelism == "scenes" and args.strong_leg == "auto":
         out["strong_scaling"] = strong_scaling_leg(world, args, 1.0)
     print(json.dumps(out), flush=True)
 
@@ -917,10 +943,20 @@ def main():
                          "makes this process the launcher of N child ranks")
     ap.add_argument("--steps", type=int, default=50, help="timed denoising steps (default: one 50-step DDIM sample)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg the headline number does not need: the other 16-bit dtype, the roofline "
+                         "leg, the batched, unipc20, dropin and dropin_varlen legs, the CPU baseline, for N > 1 the "
+                         "strong-scaling leg, and the full report file (--retune / --challenge-tiles then also cover the "
+                         "shapes of the other dtype and of the batched step).  Without it a run sets up, warms up, times "
+                         "the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the latents) as "
+                         "DIR/<name>.npy in float32, at most 64 MB in all; the same arguments give the same inputs")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"],
                     help="storage / MFMA input type of the headline number (fp32 accumulation either way).  fp16 is "
-                         "the reference's eval dtype and what BASELINE.json's metric string names; the other 16-bit "
-                         "type is measured in the same run and reported under `other_dtype` (--single-dtype skips it)")
+                         "the reference's eval dtype and what BASELINE.json's metric string names; with --full the "
+                         "other 16-bit type is measured in the same run and reported under `other_dtype` "
+                         "(--single-dtype skips it)")
     ap.add_argument("--single-dtype", action="store_true")
     ap.add_argument("--scenes", type=int, default=1, help="scenes per GPU")
     ap.add_argument("--frames", type=int, default=1,
@@ -959,14 +995,14 @@ def main():
                          "neighbour K/V exchanges between them; 'single': one graph with the point-to-point operations inside "
                          "(RCCL only); 'off': eager.  frame-split: 'single' or eager")
     ap.add_argument("--batched-scenes", type=int, default=4,
-                    help="N = 1, default workload only: ALSO time this many scenes per GPU in one batch (headline dtype, no "
+                    help="--full, N = 1, default workload only: ALSO time this many scenes per GPU in one batch (headline dtype, no "
                          "roofline leg) and report it as `batched` — the serving-throughput form of the same step (value "
                          "stays the one-scene configuration SURVEY §8d names); 0 = off")
     ap.add_argument("--no-extra-legs", action="store_true",
                     help="skip the `unipc20` (fused sampler with the reference test pipeline's UniPC-20 schedule) and `dropin` "
                          "(reference-shaped loop through the public forward() surfaces) legs of the N = 1 line")
     ap.add_argument("--strong-leg", default="auto", choices=["auto", "off"],
-                    help="N > 1 in the default scene-sharded mode: after the weak-scaling measurement rank 0 runs ONE scene "
+                    help="--full, N > 1 in the default scene-sharded mode: after the weak-scaling measurement rank 0 runs ONE scene "
                          "over all N GPUs (--parallelism view-split) as a fresh child job with a hard timeout and reports it "
                          "as `strong_scaling` in the same line (never a second line, never a hang)")
     ap.add_argument("--strong-timeout", type=float, default=float(os.environ.get("DD_STRONG_TIMEOUT", "300")),
@@ -1025,15 +1061,19 @@ def main():
     elif args.tune_cache and os.path.exists(args.tune_cache):
         O.load_tuned(args.tune_cache)
 
-    res = measure(args, args.dtype, device, dist, world, rank, backend, not args.no_roofline)
+    res = measure(args, args.dtype, device, dist, world, rank, backend, args.full and not args.no_roofline,
+                  want_outputs=args.dump_outputs is not None and rank == 0)
+    if res["outputs"] is not None:
+        dump_outputs(res["outputs"], args.dump_outputs)
+    # everything below the headline measurement runs with --full only
     other_name = "bf16" if args.dtype == "fp16" else "fp16"
     other = None
-    if not args.single_dtype and args.parallelism == "scenes":
+    if args.full and not args.single_dtype and args.parallelism == "scenes":
         other = measure(args, other_name, device, dist, world, rank, backend, False)
 
     batched = None
-    if (world == 1 and args.parallelism == "scenes" and args.scenes == 1 and args.frames == 1 and args.batched_scenes > 1
-            and not args.fp8_weights and not args.lora_rank and not args.no_graph):
+    if (args.full and world == 1 and args.parallelism == "scenes" and args.scenes == 1 and args.frames == 1
+            and args.batched_scenes > 1 and not args.fp8_weights and not args.lora_rank and not args.no_graph):
         bargs = argparse.Namespace(**vars(args))
         bargs.scenes = args.batched_scenes
         kt = os.environ.get("DD_BENCH_KERNEL_TABLE")
@@ -1058,8 +1098,8 @@ def main():
             os.environ["DD_BENCH_KERNEL_TABLE"] = kt
     # the sampler the reference's test pipeline really runs (misc/test_utils.py:161-162: UniPC, 20 steps), fused form
     unipc = dropin = dropin_varlen = None
-    if (world == 1 and args.parallelism == "scenes" and args.scenes == 1 and args.frames == 1 and not args.fp8_weights
-            and not args.lora_rank and not args.no_graph and not args.no_extra_legs):
+    if (args.full and world == 1 and args.parallelism == "scenes" and args.scenes == 1 and args.frames == 1
+            and not args.fp8_weights and not args.lora_rank and not args.no_graph and not args.no_extra_legs):
         uargs = argparse.Namespace(**vars(args))
         uargs.sampler = "unipc"
         try:
@@ -1077,7 +1117,7 @@ def main():
             dropin_varlen = dropin_varlen_leg(args, args.dtype, device, (dropin or {}).get("value"))
         except Exception as e:
             dropin_varlen = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
-    want_strong = world > 1 and args.parallelism == "scenes" and args.strong_leg == "auto"
+    want_strong = args.full and world > 1 and args.parallelism == "scenes" and args.strong_leg == "auto"
     if dist is not None:                       # the weak-scaling job is over: every rank leaves the group and frees its GPU memory
         torch.cuda.empty_cache()
         dist.barrier()
@@ -1089,7 +1129,7 @@ def main():
     if want_strong:                            # rank 0 only, as a child job: a hang or crash there cannot touch `value`
         strong = strong_scaling_leg(world, args, res["elapsed"] / args.steps * 1e3 / args.scenes)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_steps)
     pairs = res["pairs"]
     scenes_total = max(1, args.scenes * world // pairs)
@@ -1163,7 +1203,7 @@ def main():
     out["env"] = dd_env()
     if collective is not None:
         out["collective"] = collective
-    path = _write_full_report(out, "%s_n%d_%s" % (args.dtype, world, args.parallelism))
+    path = _write_full_report(out, "%s_n%d_%s" % (args.dtype, world, args.parallelism)) if args.full else None
     line = json.dumps(compact_line(out, path))
     assert len(line) < LINE_LIMIT, len(line)
     sys.stdout.flush()

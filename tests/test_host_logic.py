@@ -392,6 +392,24 @@ def test_bench_line_stays_parseable_and_short():
     assert len(fat_line) < 4096 and json.loads(fat_line)["value"] == fat["value"]
 
 
+def test_bench_dump_outputs_float32_and_fixed_sample_over_budget(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: every output as DIR/<name>.npy in float32 with its shape; an array over the byte
+    budget becomes a seeded sample of its elements that is the same in every run."""
+    import numpy as np
+    import bench
+    lat = torch.randn((1, 6, 4, 28, 50), generator=torch.Generator().manual_seed(3)).half()
+    bench.dump_outputs({"latents": lat}, str(tmp_path / "a"))
+    got = np.load(tmp_path / "a" / "latents.npy")
+    assert got.dtype == np.float32 and got.shape == (1, 6, 4, 28, 50) and np.array_equal(got, lat.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 1000)
+    big = torch.randn(5000, generator=torch.Generator().manual_seed(4))
+    for d in ("b", "c"):
+        bench.dump_outputs({"x": big}, str(tmp_path / d))
+    s1, s2 = np.load(tmp_path / "b" / "x_sample.npy"), np.load(tmp_path / "c" / "x_sample.npy")
+    assert not (tmp_path / "b" / "x.npy").exists()
+    assert s1.dtype == np.float32 and s1.shape == (1000,) and np.array_equal(s1, s2) and np.isin(s1, big.numpy()).all()
+
+
 def test_pmc_summary_counts_only_the_timed_steps(tmp_path):
     """HBM traffic per launch must come from the dispatches of the timed steps, per launch shape —
     not from every dispatch of a symbol in the process (tuner launches behind a 320 MB flush were charged the flush's

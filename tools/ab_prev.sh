@@ -13,6 +13,6 @@ OUT=gpurun_out/${TAG}_ab.txt; rm -f $OUT
 for i in $(seq 1 $N); do
   for v in new prev; do
     if [ $v = prev ]; then export DD_HIP_LIB=$PWD/dualdiff_amd/lib/libdd_prev.so; else unset DD_HIP_LIB; fi
-    timeout 300 python bench.py --steps 30 --warmup 5 --no-roofline --no-cpu-baseline --no-extra-legs 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('lib=$v', round(d['value'],2), round(d['other_dtype']['value'],2), round(d['batched']['value'],2), d['outputs_finite'])" | tee -a $OUT
+    timeout 300 python bench.py --full --steps 30 --warmup 5 --no-roofline --no-cpu-baseline --no-extra-legs 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('lib=$v', round(d['value'],2), round(d['other_dtype']['value'],2), round(d['batched']['value'],2), d['outputs_finite'])" | tee -a $OUT
   done
 done

@@ -3,8 +3,8 @@
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
 NEW=gpurun_out/tuned_challenge.json
 cp dualdiff_amd/tuned/gfx950.json $NEW
-python bench.py --challenge-tiles $1 --tune-cache $NEW --steps 5 --warmup 2 --no-cpu-baseline --no-roofline 2>/dev/null | grep "^\[tune\]" > gpurun_out/r03h_challenge.log
-wc -l gpurun_out/r03h_challenge.log
+python bench.py --full --challenge-tiles $1 --tune-cache $NEW --steps 5 --warmup 2 --no-cpu-baseline --no-roofline 2>/dev/null | grep "^\[tune\]" > "${NEW%.json}.log"
+wc -l "${NEW%.json}.log"
 for i in 1 2 3 4; do
   for t in old new; do
     if [ $t = new ]; then export DD_TUNE_TABLE=$GRAFT_REPO_ROOT/$NEW; else unset DD_TUNE_TABLE; fi

@@ -9,8 +9,8 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-# 1. the bench line (default command of the driver + the per-class table)
-DD_BENCH_KERNEL_TABLE=$OUT/${TAG}_classes.txt python3 $R/bench.py --steps 30 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+# 1. the bench line with every leg (--full: roofline, other dtype, batched, CPU baseline, ...) + the per-class table
+DD_BENCH_KERNEL_TABLE=$OUT/${TAG}_classes.txt python3 $R/bench.py --full --steps 30 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 # 2. kernel trace + stats of the same command (graph replay, 3 streams)
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/${TAG}_kt -o kt -- \
   python3 $R/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-roofline --single-dtype --batched-scenes 0 --no-extra-legs \

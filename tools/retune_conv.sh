@@ -17,6 +17,6 @@ OUT=gpurun_out/r05_retune_conv_ab.txt; rm -f $OUT
 for i in 1 2 3; do
   for t in old new; do
     if [ $t = new ]; then export DD_TUNE_TABLE=$PWD/gpurun_out/tuned_conv_new.json; else unset DD_TUNE_TABLE; fi
-    timeout 300 python bench.py --steps 30 --warmup 5 --no-roofline --no-cpu-baseline --no-extra-legs 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('table=$t', round(d['value'],2), round(d['other_dtype']['value'],2), round(d['batched']['value'],2), d['outputs_finite'])" | tee -a $OUT
+    timeout 300 python bench.py --full --steps 30 --warmup 5 --no-roofline --no-cpu-baseline --no-extra-legs 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('table=$t', round(d['value'],2), round(d['other_dtype']['value'],2), round(d['batched']['value'],2), d['outputs_finite'])" | tee -a $OUT
   done
 done
