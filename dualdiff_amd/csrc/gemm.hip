@@ -43,7 +43,7 @@ struct GemmParams {
   int band_rows, bands; float inv_bands; // ... its BAND form: output pixels per band, bands per instance
   const float* ln_colsum; const float* ln_bias; float ln_eps;   // LayerNorm fold (dd_gemm2_kernel, dense)
   int out_f32;                           // store fp32 instead of T
-  float* stat_out;                       // [rows][n/32][2] row sum / sum of squares of the stored values, or NULL
+  float* stat_out;                       // [rows][n/32][2] row sum / sum of squares of the fp32 values before their rounding to T, or NULL
   const float* stat_in;                  // LayerNorm fold: [rows][k/32][2] table of the `a` rows, or NULL
   int hm_d, hm_planes; float hm_scale;   // head-major output: plane width D, scaled planes, their factor
   int persist;                           // dd_gemm2_kernel: the grid is smaller than the tile count (see the kernel)
@@ -2565,6 +2565,10 @@ Plan make_plan(const dd_gemm_desc* d) {
     ti = alt;
   }
   const TileCfg& t = kTiles[ti];
+  // forms launch_tile instantiates no kernel for: GEGLU on a tile whose waves hold two 16-column blocks (the h / gate
+  // halves need four), a convolution on the 32-row and whole-row (LayerNorm-emitting) tiles.  Planned as unsupported, so
+  // that dd_gemm_kernel_name never names a kernel dd_gemm then refuses.
+  if ((geglu && t.tn % 4 != 0) || (d->conv && (t.id == 40 || t.id == 59 || t.id == 60))) { pl.unsupported = true; return pl; }
   const int bn_out = geglu ? tile_bn(t) / 2 : tile_bn(t);
   pl.tile_idx = ti;
   pl.tiles_m = ceil_div(d->rows, tile_bm(t));

@@ -217,13 +217,8 @@ def _autotune(lib, d, key, out_shape, dtype, device, warm=()):
     saved = (d.out, d.ldc, d.accumulate, d.tile, d.split_k, d.ws, d.ws_bytes)
     scratch = torch.empty(out_shape, dtype=dtype, device=device)
     d.out, d.ldc, d.accumulate = scratch.data_ptr(), scratch.stride(0), 0
-    kt = (d.k + 63) // 64
-    blocks128 = ((d.rows + 127) // 128) * ((d.n + 127) // 128)
     best, best_t = (0, 0, 0), float("inf")
     stream = _stream()
-    global _TILES
-    if _TILES is None:
-        _TILES = tuple(lib.dd_gemm_tile_id(i) for i in range(lib.dd_gemm_num_tiles()))
 
     def timed(tile, split, iters, ink=0):          # ink: third entry of a table row (split-K form), always 0 since round 5
         d.tile, d.split_k = tile, split
@@ -271,16 +266,13 @@ def _autotune(lib, d, key, out_shape, dtype, device, warm=()):
         return best
     cands = []
     excl = {int(t) for t in _os.environ.get("DD_TUNE_EXCLUDE", "").split(",") if t.strip()}   # A/B experiments
-    for tile in _TILES:
+    for tile, split in tune_candidates(lib, d):
         if tile in excl:
             continue
-        for split in _SPLITS:
-            if split > 1 and (d.epilogue == DD_EPI_GEGLU or kt < 4 * split or blocks128 * split > 4096):
-                continue
-            for ink in (0,):
-                t = timed(tile, split, 3, ink)            # >= 3 samples per candidate, cold or hot
-                if t is not None:
-                    cands.append((t, tile, split, ink))
+        for ink in (0,):
+            t = timed(tile, split, 3, ink)            # >= 3 samples per candidate, cold or hot
+            if t is not None:
+                cands.append((t, tile, split, ink))
     # the coarse pass is noisy: re-time the front-runners with more launches
     cands.sort()
     for t, tile, split, ink in cands[:8]:
@@ -288,8 +280,25 @@ def _autotune(lib, d, key, out_shape, dtype, device, warm=()):
         if t2 is not None and t2 < best_t:
             best, best_t = (tile, split, ink), t2
     (d.out, d.ldc, d.accumulate, d.tile, d.split_k, d.ws, d.ws_bytes) = saved
+    if best[0] == 0:
+        # no candidate launched: the call is one no kernel can run.  Caching (0, 0, 0) would let save_tuned() write
+        # it into the tracked table; the call itself goes on to the library's own plan and raises from there.
+        return best
     _TUNED[key] = best
     return best
+
+
+def tune_candidates(lib, d):
+    """(tile id, split-K) pairs the run-time tuner times for the call described by `d` — every tile of the library,
+    split-K only where the K loop keeps >= 4 steps per slab and the slabs stay within 4096 128x128 blocks.  The planner
+    may still turn a pair down (dd_gemm_kernel_name: "unsupported") or launch it in a normalised form."""
+    global _TILES
+    if _TILES is None:
+        _TILES = tuple(lib.dd_gemm_tile_id(i) for i in range(lib.dd_gemm_num_tiles()))
+    kt = (d.k + 63) // 64
+    blocks128 = ((d.rows + 127) // 128) * ((d.n + 127) // 128)
+    return [(tile, split) for tile in _TILES for split in _SPLITS
+            if split == 1 or not (d.epilogue == DD_EPI_GEGLU or kt < 4 * split or blocks128 * split > 4096)]
 
 
 def set_timer(t):

@@ -135,7 +135,8 @@ typedef struct dd_gemm_desc {
                           rounded to the storage type before the softmax); no GEGLU / accumulate */
   /* LayerNorm statistics carried from the producer to the consumer (both optional, fp32):
    * ln_stats_out: this GEMM's epilogue also writes, per output row and per 32-column group, the sum and the
-   *   sum of squares of the values it stores: [rows][n / 32][2] (n % 32 == 0, no split-K, no GEGLU).  Every
+   *   sum of squares of the values it stores, taken in fp32 before their rounding to the storage type (so a
+   *   consumer normalises with the statistics of the unrounded result): [rows][n / 32][2] (n % 32 == 0, no split-K, no GEGLU).  Every
    *   transformer-block GEMM whose output feeds a LayerNorm (proj_in, to_out + residual; blocks.py:150-236)
    *   holds those values in registers anyway.
    * ln_stats_in: with the LayerNorm fold above, the row mean / rstd come from such a table of the `a`
