@@ -149,6 +149,13 @@ SIGNATURES = {
                                   c_int32, c_int32, c_int32, c_void_p]),
     "dd_cfg_ddim_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                    c_int64, c_int32, c_void_p]),
+    "dd_cfg_ddim_step_given": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int32, c_void_p]),
+    "dd_cfg_unipc_step_given": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64,
+                                          c_int64, c_int32, c_void_p]),
+    "dd_given_views_noise": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int64,
+                                       c_int64, c_int32, c_void_p]),
 }
 
 ABI_VERSION = 4

@@ -4,6 +4,7 @@ Every function launches hand-written gfx950 kernels from libdualdiff_hip.so on t
 current stream.  Tensors are token-major / NHWC 2-D views (rows, channels) in fp16 or bf16.
 There is no eager fallback: a non-GPU tensor raises.
 """
+import collections as _collections
 import ctypes
 import threading as _threading
 
@@ -1030,31 +1031,89 @@ def conv3x3_small_cout(x, w, bias, m, h, wd, out=None):
     return out
 
 
-def cfg_ddim_step(eps, x, coef, guidance, x_out=None, x_dup=None):
-    """eps: (2, n...) uncond first; x: (n...); coef: fp32 device [4]."""
+class GivenViews(_collections.namedtuple("GivenViews", "mask clean noise0 gcoef mode")):
+    """Given-view state of the fused sampler step (pipeline_bev_controlnet_given_view.py; include/dualdiff_hip.h):
+    mask   uint8 device (views,), non-zero for a given view-instance (the latents are `views` equal blocks);
+    clean  fp32 device (n...), the clean latents of the given views (any values elsewhere);
+    noise0 device (n...) in the latents' dtype, the latents at loop entry;
+    gcoef  fp32 device [3], the current row of schedulers.given_view_table (refreshed between graph replays);
+    mode   1: re-noise the given views every step (conditional_latents_change_every_input=True), 2: fixed noise."""
+
+
+def _given_args(g, x):
+    _need_gpu(g.mask, g.clean, g.noise0, g.gcoef)
+    if g.mode not in (1, 2):
+        raise ValueError("given-view mode is 1 (change every input) or 2 (fixed noise), got %r" % (g.mode,))
+    if g.mask.dtype != torch.uint8 or g.mask.dim() != 1 or not g.mask.is_contiguous() or g.mask.numel() == 0:
+        raise ValueError("given-view mask must be a contiguous uint8 vector with one byte per view-instance")
+    if x.numel() % g.mask.numel():
+        raise ValueError("%d latent elements are not %d equal views" % (x.numel(), g.mask.numel()))
+    if g.clean.dtype != torch.float32 or g.clean.numel() != x.numel() or not g.clean.is_contiguous():
+        raise ValueError("given-view clean latents must be contiguous fp32 with the latents' %d elements" % x.numel())
+    if g.noise0.dtype != x.dtype or g.noise0.numel() != x.numel() or not g.noise0.is_contiguous():
+        raise ValueError("given-view noise0 must be contiguous, in the latents' dtype, with their %d elements" % x.numel())
+    if g.gcoef.dtype != torch.float32 or g.gcoef.numel() < 3:
+        raise ValueError("given-view gcoef must be a fp32 device row of 3")
+    return x.numel() // g.mask.numel()
+
+
+def cfg_ddim_step(eps, x, coef, guidance, x_out=None, x_dup=None, given=None):
+    """eps: (2, n...) uncond first; x: (n...); coef: fp32 device [4].
+    given: None (the plain step) or a GivenViews — dd_cfg_ddim_step_given."""
     lib = _native.load()
     _need_gpu(eps, x, coef, x_out, x_dup)
     if x_out is None:
         x_out = torch.empty_like(x)
-    rc = lib.dd_cfg_ddim_step(_ptr(eps), _ptr(x), _ptr(x_out), _ptr(x_dup), _ptr(coef),
-                              float(guidance), x.numel(), _dt(x), _stream())
-    _native.check(rc, "cfg_ddim_step")
+    if given is None:
+        rc = lib.dd_cfg_ddim_step(_ptr(eps), _ptr(x), _ptr(x_out), _ptr(x_dup), _ptr(coef),
+                                  float(guidance), x.numel(), _dt(x), _stream())
+        _native.check(rc, "cfg_ddim_step")
+        return x_out
+    ve = _given_args(given, x)
+    rc = lib.dd_cfg_ddim_step_given(_ptr(eps), _ptr(x), _ptr(x_out), _ptr(x_dup), _ptr(coef), float(guidance),
+                                    _ptr(given.mask), _ptr(given.clean), _ptr(given.noise0), _ptr(given.gcoef),
+                                    int(given.mode), x.numel(), ve, _dt(x), _stream())
+    _native.check(rc, "cfg_ddim_step_given")
     return x_out
 
 
-def cfg_unipc_step(eps, x, hist, coef, guidance, x_out=None, x_dup=None):
+def cfg_unipc_step(eps, x, hist, coef, guidance, x_out=None, x_dup=None, given=None):
     """eps: (2, n...) uncond first; x: (n...); hist: fp32 (3, n...) = [last, m1, m2] updated in place;
-    coef: fp32 device [10] (dualdiff_amd.pipeline.schedulers.unipc_schedule row)."""
+    coef: fp32 device [10] (dualdiff_amd.pipeline.schedulers.unipc_schedule row).
+    given: None (the plain step) or a GivenViews — dd_cfg_unipc_step_given."""
     lib = _native.load()
     _need_gpu(eps, x, hist, coef, x_out, x_dup)
     if hist.dtype != torch.float32 or hist.shape[0] != 3 or hist[0].numel() != x.numel() or not hist.is_contiguous():
         raise ValueError("hist must be a contiguous fp32 (3, n...) tensor")
     if x_out is None:
         x_out = torch.empty_like(x)
-    rc = lib.dd_cfg_unipc_step(_ptr(eps), _ptr(x), _ptr(x_out), _ptr(x_dup), _ptr(hist[0]), _ptr(hist[1]),
-                               _ptr(hist[2]), _ptr(coef), float(guidance), x.numel(), _dt(x), _stream())
-    _native.check(rc, "cfg_unipc_step")
+    if given is None:
+        rc = lib.dd_cfg_unipc_step(_ptr(eps), _ptr(x), _ptr(x_out), _ptr(x_dup), _ptr(hist[0]), _ptr(hist[1]),
+                                   _ptr(hist[2]), _ptr(coef), float(guidance), x.numel(), _dt(x), _stream())
+        _native.check(rc, "cfg_unipc_step")
+        return x_out
+    ve = _given_args(given, x)
+    rc = lib.dd_cfg_unipc_step_given(_ptr(eps), _ptr(x), _ptr(x_out), _ptr(x_dup), _ptr(hist[0]), _ptr(hist[1]),
+                                     _ptr(hist[2]), _ptr(coef), float(guidance), _ptr(given.mask), _ptr(given.clean),
+                                     _ptr(given.noise0), _ptr(given.gcoef), int(given.mode), x.numel(), ve, _dt(x),
+                                     _stream())
+    _native.check(rc, "cfg_unipc_step_given")
     return x_out
+
+
+def given_views_noise(x, given, t0, x_dup=None):
+    """x[v] (and x_dup[v]) = add_noise(clean, noise0, timesteps[0]) on the given views of `given` (a GivenViews; its
+    gcoef and mode are not used), in place; t0 = schedulers.given_view_table(...)[0] (host or device, 2 values)."""
+    lib = _native.load()
+    _need_gpu(x, x_dup)
+    ve = _given_args(given, x)
+    if x_dup is not None and (x_dup.dtype != x.dtype or x_dup.numel() != x.numel()):
+        raise ValueError("x_dup must match x")
+    sa, s1a = (float(v) for v in t0.tolist()[:2])
+    rc = lib.dd_given_views_noise(_ptr(x), _ptr(x_dup), _ptr(given.mask), _ptr(given.clean), _ptr(given.noise0),
+                                  sa, s1a, x.numel(), ve, _dt(x), _stream())
+    _native.check(rc, "given_views_noise")
+    return x
 
 
 def softmax_rows(s, dtype, pad_to=8):

@@ -23,7 +23,7 @@ from typing import List, Optional
 import torch
 
 from .. import ops as O
-from .schedulers import unipc_schedule
+from .schedulers import given_view_table, unipc_schedule
 
 
 def ddim_schedule(num_inference_steps, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012,
@@ -41,6 +41,54 @@ def ddim_schedule(num_inference_steps, num_train_timesteps=1000, beta_start=0.00
         a_p = acp[prev] if prev >= 0 else (torch.tensor(1.0, dtype=torch.float64) if set_alpha_to_one else acp[0])
         coefs.append([a_t.sqrt(), (1 - a_t).sqrt(), a_p.sqrt(), (1 - a_p).sqrt()])
     return ts, torch.tensor(coefs, dtype=torch.float32)
+
+
+def given_view_inputs(conditional_latents, shape, mask=None, device=None):
+    """Given-view inputs (pipeline_bev_controlnet_given_view.py:33-36) -> (clean, given): clean fp32 (b, n, c, h, w)
+    (zeros on views that are not given), given bool (b, n), both on `device` (default: that of the inputs).
+
+    `shape` is the latents' (b, n, c, h, w).  Accepted: the reference's b x n list of lists whose entries are (c, h, w)
+    tensors or None, in any float dtype and on any device (`mask` must then be None); or a (b, n, c, h, w) tensor
+    with a boolean (b, n) `mask`.  A wrong b / n / c / h / w raises ValueError naming the offending entry."""
+    b, n, c, h, w = (int(v) for v in shape)
+    if torch.is_tensor(conditional_latents):
+        if mask is None:
+            raise ValueError("conditional_latents given as a tensor needs conditional_mask (b, n)")
+        if tuple(conditional_latents.shape) != (b, n, c, h, w):
+            raise ValueError("conditional_latents has shape %s, the latents %s"
+                             % (tuple(conditional_latents.shape), (b, n, c, h, w)))
+        if not torch.is_tensor(mask) or tuple(mask.shape) != (b, n) or mask.dtype != torch.bool:
+            raise ValueError("conditional_mask must be a boolean (%d, %d) tensor, got %s"
+                             % (b, n, tuple(mask.shape) if torch.is_tensor(mask) else type(mask).__name__))
+        dev = device if device is not None else conditional_latents.device
+        return conditional_latents.to(dev, torch.float32), mask.to(dev)
+    if mask is not None:
+        raise ValueError("conditional_mask goes with a (b, n, c, h, w) conditional_latents tensor, not a list of lists")
+    if len(conditional_latents) != b:
+        raise ValueError("conditional_latents has %d rows, the latents b = %d" % (len(conditional_latents), b))
+    dev = device
+    for i, row in enumerate(conditional_latents):
+        if row is None or len(row) != n:
+            raise ValueError("conditional_latents[%d] has %s entries, the latents n = %d"
+                             % (i, "no" if row is None else len(row), n))
+        for j, c_ij in enumerate(row):
+            if c_ij is None:
+                continue
+            if not torch.is_tensor(c_ij) or not c_ij.is_floating_point() or tuple(c_ij.shape) != (c, h, w):
+                raise ValueError("conditional_latents[%d][%d] is %s, expected a float (%d, %d, %d) tensor"
+                                 % (i, j, tuple(c_ij.shape) if torch.is_tensor(c_ij) else type(c_ij).__name__,
+                                    c, h, w))
+            if dev is None:
+                dev = c_ij.device
+    dev = dev if dev is not None else torch.device("cpu")
+    clean = torch.zeros((b, n, c, h, w), dtype=torch.float32, device=dev)
+    given = torch.zeros((b, n), dtype=torch.bool, device=dev)
+    for i, row in enumerate(conditional_latents):
+        for j, c_ij in enumerate(row):
+            if c_ij is not None:
+                clean[i, j] = c_ij.to(dev, torch.float32)
+                given[i, j] = True
+    return clean, given
 
 
 class BEVDenoiser:
@@ -71,6 +119,7 @@ class BEVDenoiser:
         self._graph = None
         self._prepared = None
         self._segmented = False
+        self._given = None                  # ops.GivenViews of the current inputs (set_inputs' conditional_latents)
         # view split + use_graph: record the step as graph SEGMENTS with the exchanges between them (default) instead of
         # one graph that would have to contain the point-to-point operations
         self.segmented_graph = bool(segmented_graph)
@@ -105,14 +154,31 @@ class BEVDenoiser:
         self.frame_shard = frame_shard if frame_shard is not None else getattr(unet, "frame_shard", None)
 
     # ---------------------------------------------------------------------------- inputs ----
-    def set_inputs(self, latents, prompt_embeds, camera_param, bboxes_list, conds):
+    def set_inputs(self, latents, prompt_embeds, camera_param, bboxes_list, conds, conditional_latents=None,
+                   conditional_latents_change_every_input=True, conditional_mask=None):
         """latents (b, n, 4, h, w); prompt_embeds (2b, L, 768), camera_param (2b, n, 3, 7),
         bboxes_list[i] dict of (2b, n|1, N, ...), conds[i] (2b, 3, 224, 2400) or (2b*n, 320, h, w):
-        all with the unconditional half FIRST (pipeline_bev_controlnet.py:349-375)."""
+        all with the unconditional half FIRST (pipeline_bev_controlnet.py:349-375).
+
+        Given views (StableDiffusionBEVControlNetGivenViewPipeline): `conditional_latents` holds the clean latents of
+        the views to hold fixed — the reference's b x n list of lists of (4, h, w) tensors or None, or a
+        (b, n, 4, h, w) tensor with a boolean (b, n) `conditional_mask` (given_view_inputs) — over the FULL inputs
+        (all frames, all views), sliced like `latents` under a frame / view shard.  Every given view v is set to
+        add_noise(c[v], n0[v], timesteps[0]) here (n0: `latents`), then each step
+          conditional_latents_change_every_input=True:  stores add_noise(c[v], n0[v], t_next) for the next step's
+                                                        input (not after the last step);
+          False:                                        replaces v's guided noise by n0[v] before the update;
+        both inside the fused CFG + scheduler kernel.  add_noise is fp32 arithmetic on the fp32 clean latents,
+        rounded once to the model dtype: for fp32 conditional latents this matches the reference's (computed in their
+        dtype, then `.type_as(latents)`) to within 1 ulp of the model dtype.  None or all entries None: the plain
+        sampler, bit for bit."""
         dev = latents.device
         if not latents.is_cuda:
             raise RuntimeError("BEVDenoiser runs on the GPU only")
         dt = self.unet.dtype
+        clean = gmask = None
+        if conditional_latents is not None:
+            clean, gmask = given_view_inputs(conditional_latents, latents.shape, conditional_mask, device=dev)
         fs = self.frame_shard
         if fs is not None:                                              # keep this rank's frames of every input
             t_all = fs.plan.n_frames
@@ -120,6 +186,8 @@ class BEVDenoiser:
                 raise ValueError("%d batch entries are not scenes x %d frames" % (latents.shape[0], t_all))
             sc, n_all = latents.shape[0] // t_all, latents.shape[1]
             latents = fs.take_frames(latents, sc, 1)
+            if clean is not None:
+                clean, gmask = fs.take_frames(clean, sc, 1), fs.take_frames(gmask, sc, 1)
             prompt_embeds = fs.take_frames(prompt_embeds, 2 * sc, 1)    # [uncond ; cond] x scenes x frames
             camera_param = fs.take_frames(camera_param, 2 * sc, 1)
             bboxes_list = [None if d is None else {k: fs.take_frames(v, 2 * sc, 1) for k, v in d.items()}
@@ -129,6 +197,8 @@ class BEVDenoiser:
         if vs is not None:                                              # keep this rank's views of every input
             n_all = latents.shape[1]
             latents = vs.take_views(latents, 1, n_all)
+            if clean is not None:
+                clean, gmask = vs.take_views(clean, 1, n_all), vs.take_views(gmask, 1, n_all)
             camera_param = vs.take_views(camera_param, 1, n_all)
             bboxes_list = [None if d is None else {k: vs.take_views(v, 1, n_all) for k, v in d.items()}
                            for d in bboxes_list]
@@ -154,9 +224,23 @@ class BEVDenoiser:
         self.bboxes_list = bboxes_list
         self.conds = conds
         self.t_table = self.timesteps.to(dev, torch.float32)[:, None].expand(-1, self.m).contiguous()
-        self.coef_dev = self.coef_table.to(dev)
+        self._given = None
+        rows = self.coef_table
+        if gmask is not None and bool(gmask.any()):                     # given views (all None: the plain sampler)
+            t0, gtab = given_view_table(self.timesteps)
+            rows = torch.cat([rows, gtab], dim=1)                       # the gcoef row rides in the coef copy
+        self.coef_dev = rows.to(dev)
         self.t_dev = torch.empty(self.m, dtype=torch.float32, device=dev)
-        self.coef = torch.empty(self.coef_table.shape[1], dtype=torch.float32, device=dev)
+        self.coef = torch.empty(rows.shape[1], dtype=torch.float32, device=dev)
+        if rows is not self.coef_table:
+            self._given = O.GivenViews(
+                mask=gmask.reshape(b * n).to(torch.uint8).contiguous(),
+                clean=clean.reshape(b * n, c, h, w).contiguous(),
+                noise0=self.lat2[0].clone(),                            # original_noise (given_view.py:264)
+                gcoef=self.coef[self.coef_table.shape[1]:],
+                mode=1 if conditional_latents_change_every_input else 2)
+            # before capture() snapshots lat2: its warm-ups and restores keep the noised given views
+            O.given_views_noise(self.lat2[0], self._given, t0, x_dup=self.lat2[1])
         self.hist = torch.zeros((3, b * n, c, h, w), dtype=torch.float32, device=dev) if self.sampler == "unipc" else None
         self._graph = None
         self._prepared = None
@@ -171,7 +255,7 @@ class BEVDenoiser:
 
     def _set_step(self, i):
         self.t_dev.copy_(self.t_table[i], non_blocking=True)
-        self.coef.copy_(self.coef_dev[i], non_blocking=True)
+        self.coef.copy_(self.coef_dev[i], non_blocking=True)            # with the given views' gcoef row, if any
 
     # ------------------------------------------------------------------------------ step ----
     def _step_body(self):
@@ -242,10 +326,10 @@ class BEVDenoiser:
     def _scheduler_step(self, eps2):
         if self.sampler == "ddim":
             O.cfg_ddim_step(eps2, self.lat2[0], self.coef, self.guidance_scale,
-                            x_out=self.lat2[0], x_dup=self.lat2[1])
+                            x_out=self.lat2[0], x_dup=self.lat2[1], given=self._given)
         else:
             O.cfg_unipc_step(eps2, self.lat2[0], self.hist, self.coef, self.guidance_scale,
-                             x_out=self.lat2[0], x_dup=self.lat2[1])
+                             x_out=self.lat2[0], x_dup=self.lat2[1], given=self._given)
 
     def _combine_halves(self):
         """CFG split: exchange the two halves' noise predictions, then guidance + DDIM on both ranks

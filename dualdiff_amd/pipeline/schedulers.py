@@ -98,3 +98,25 @@ def unipc_schedule(num_inference_steps, num_train_timesteps=1000, beta_start=0.0
         if lower_order_nums < solver_order:
             lower_order_nums += 1
     return torch.from_numpy(ts.copy()), torch.tensor(rows, dtype=torch.float64).to(torch.float32)
+
+
+def given_view_table(timesteps, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, dtype=torch.float32):
+    """Given-view sampling (pipeline_bev_controlnet_given_view.py): the add_noise coefficients of a sampler's own
+    `timesteps` (DDIM's with steps_offset, UniPC's de-duplicated), from the same scaled-linear betas as
+    `ddim_schedule` / `unipc_schedule`, built in float64.
+
+    Returns (t0, gcoef):
+      t0     (2,)       {sqrt(acp[timesteps[0]]), sqrt(1 - acp[timesteps[0]])}: the pre-loop noising (dd_given_views_noise);
+      gcoef  (steps, 3) row i = {sqrt(acp[t_next]), sqrt(1 - acp[t_next]), renoise} for step i's fused store, t_next =
+                        timesteps[i + 1]; renoise = 0 on the last row, whose t_next is 0 — the sample both samplers end
+                        on (DDIM with set_alpha_to_one=False steps to acp[0], UniPC to t = 0).
+    """
+    alpha, sigma, _ = _sd_tables(num_train_timesteps, beta_start, beta_end)
+    ts = [int(t) for t in (timesteps.tolist() if hasattr(timesteps, "tolist") else timesteps)]
+    if not ts:
+        raise ValueError("given_view_table needs at least one timestep")
+    nxt = ts[1:] + [0]
+    rows = [[alpha[t], sigma[t], 1.0] for t in nxt]
+    rows[-1][2] = 0.0
+    t0 = torch.tensor([alpha[ts[0]], sigma[ts[0]]], dtype=torch.float64).to(dtype)
+    return t0, torch.tensor(rows, dtype=torch.float64).to(dtype)

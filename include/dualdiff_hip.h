@@ -438,6 +438,40 @@ int dd_cfg_unipc_step(const void* eps, const void* x, void* x_out, void* x_dup, 
                       float* m2, const float* coef, float guidance, int64_t n, int32_t dtype,
                       dd_stream_t stream);
 
+/* Given-view sampling (pipeline/pipeline_bev_controlnet_given_view.py: some views are held to clean latents c
+ * the caller supplies, the sampler generates the others).  add_noise(c, n0, t) = sqrt(acp[t]) c + sqrt(1-acp[t]) n0
+ * (scheduler.add_noise) is evaluated in fp32 on fp32 c and rounded once to the storage type T.
+ * The views are the n / view_elems consecutive blocks of view_elems elements (the view-instances of x);
+ * given: device bytes, one per view-instance, non-zero for a given view; clean: fp32 [n] (c of the given views, any
+ * values elsewhere); noise0: [n] in T, the latents at loop entry (original_noise, :264).
+ *
+ * dd_cfg_ddim_step_given / dd_cfg_unipc_step_given: dd_cfg_ddim_step / dd_cfg_unipc_step (same arguments, same
+ * arithmetic, bit-identical results on views whose byte is 0) plus, on the given views:
+ *   mode 1 (conditional_latents_change_every_input = True, :283-295): the step stores add_noise(c, n0, t_next) in
+ *     x_out and x_dup instead of the update — the overwrite at the top of the NEXT step, fused into this step's
+ *     store.  gcoef: device fp32[3] = {sqrt(acp[t_next]), sqrt(1-acp[t_next]), renoise} read at kernel time (graph
+ *     replay); renoise = 0 on the last step, which stores the update (nothing is overwritten after the loop).  The
+ *     UniPC history is advanced from the step's input x as on every other view.
+ *   mode 2 (change_every_input = False, :380-389): the guided noise is replaced by n0 before the update (gcoef unused,
+ *     but must be a valid pointer).
+ * Grid: one blockIdx.y per view-instance (n / view_elems <= 65535, view_elems < 2^31, else DD_ERR_UNSUPPORTED).
+ * DD_ERR_BAD_ARG: a NULL pointer (x_dup may be NULL), view_elems <= 0 or not dividing n, mode not 1 or 2, dtype. */
+int dd_cfg_ddim_step_given(const void* eps, const void* x, void* x_out, void* x_dup, const float* coef,
+                           float guidance, const uint8_t* given, const float* clean, const void* noise0,
+                           const float* gcoef, int32_t mode, int64_t n, int64_t view_elems, int32_t dtype,
+                           dd_stream_t stream);
+int dd_cfg_unipc_step_given(const void* eps, const void* x, void* x_out, void* x_dup, float* last, float* m1,
+                            float* m2, const float* coef, float guidance, const uint8_t* given, const float* clean,
+                            const void* noise0, const float* gcoef, int32_t mode, int64_t n, int64_t view_elems,
+                            int32_t dtype, dd_stream_t stream);
+
+/* The pre-loop noising of the given views (:265-276 in mode 2; the first step's overwrite :283-295 in mode 1):
+ * x[v] = x_dup[v] = add_noise(c, n0, timesteps[0]) on the given views, other views untouched; sqrt_acp / sqrt_1m_acp
+ * are sqrt(acp[timesteps[0]]) and sqrt(1 - acp[timesteps[0]]).  x_dup may be NULL.  Once per sample, before step 0. */
+int dd_given_views_noise(void* x, void* x_dup, const uint8_t* given, const float* clean, const void* noise0,
+                         float sqrt_acp, float sqrt_1m_acp, int64_t n, int64_t view_elems, int32_t dtype,
+                         dd_stream_t stream);
+
 /* ------------------------------------------------------------------------- *
  * EXTENSION (BASELINE configs[4]: "fp8 weights (CDNA4 fp8 MFMA)"; no reference semantics — README.md:47-49 is prose):
  * W8A8 projection on the fp8 matrix path.
