@@ -104,6 +104,9 @@ SIGNATURES = {
     "dd_gemm_num_tiles": (c_int32, []),
     "dd_gemm_tile_id": (c_int32, [c_int32]),
     "dd_gemm_kernel_name": (c_char_p, [POINTER(GemmDesc)]),
+    "dd_gemm_conv_pad": (c_int32, [POINTER(GemmDesc), c_int32, c_void_p]),
+    "dd_gemm_conv_pad_workspace_bytes": (c_int64, [POINTER(GemmDesc), c_int32]),
+    "dd_gemm_conv_pad_kernel_name": (c_char_p, [POINTER(GemmDesc), c_int32]),
     "dd_groupnorm_nhwc": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                     c_int32, c_int32, c_int32, c_float, c_int32, c_int32,
                                     c_void_p, c_int64, c_void_p]),
@@ -145,6 +148,8 @@ SIGNATURES = {
                                    c_int32, c_int32, c_void_p]),
     "dd_conv3x3_small_cout": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                         c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "dd_vae_posterior": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float,
+                                   c_int32, c_int32, c_void_p]),
     "dd_conv3x3_thin": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                   c_int32, c_int32, c_int32, c_void_p]),
     "dd_cfg_ddim_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,

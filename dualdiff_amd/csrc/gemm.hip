@@ -346,9 +346,12 @@ __device__ __forceinline__ void store_tile(const GemmParams& p, f32x4 (&acc)[TN]
   }
 }
 
-template <typename T, int WAVES_M, int WAVES_N, int TM, int TN, bool CONV, bool GEGLU>
-__global__ __launch_bounds__(64 * WAVES_M * WAVES_N)
-void dd_gemm_kernel(const GemmParams p) {
+// PAD_LO: top / left zero padding of the conv gather — output pixel o reads input rows / columns o*stride - PAD_LO + 0..2.
+// 1 is nn.Conv2d(padding=1); 0 (stride 2 only) is diffusers' Downsample2D(padding=0), F.pad(x, (0, 1, 0, 1)) then a
+// 3x3 / stride 2 / pad 0 conv: its bottom / right pad is the "outside the stored image reads zero" rule every conv has.
+// The kernels are thin __global__ wrappers around this body, so the PAD_LO = 1 symbols are the ones of before.
+template <typename T, int WAVES_M, int WAVES_N, int TM, int TN, bool CONV, bool GEGLU, int PAD_LO>
+__device__ __forceinline__ void gemm1_body(const GemmParams& p) {
   using V8 = typename dd_vec<T>::v8;
   constexpr int NT = 64 * WAVES_M * WAVES_N;
   constexpr int BM = WAVES_M * TM * 16;
@@ -399,8 +402,8 @@ void dd_gemm_kernel(const GemmParams p) {
         const int oy = dd_fdiv(rem, p.inv_wout);
         const int ox = rem - oy * p.wout;
         xm[i] = inst;
-        xiy[i] = oy * p.stride - 1;
-        xix[i] = ox * p.stride - 1;
+        xiy[i] = oy * p.stride - PAD_LO;
+        xix[i] = ox * p.stride - PAD_LO;
       } else {
         xm[i] = r; xiy[i] = 0; xix[i] = 0;
       }
@@ -535,6 +538,19 @@ void dd_gemm_kernel(const GemmParams p) {
   }
 
   store_tile<T, TM, TN, GEGLU>(p, acc, block_m0, block_n0, wave_m, wave_n, lane, p.rows);
+}
+
+template <typename T, int WAVES_M, int WAVES_N, int TM, int TN, bool CONV, bool GEGLU>
+__global__ __launch_bounds__(64 * WAVES_M * WAVES_N)
+void dd_gemm_kernel(const GemmParams p) {
+  gemm1_body<T, WAVES_M, WAVES_N, TM, TN, CONV, GEGLU, 1>(p);
+}
+
+// conv with PAD_LO = 0 (Downsample2D(padding=0) of the VAE encoder's down blocks)
+template <typename T, int WAVES_M, int WAVES_N, int TM, int TN>
+__global__ __launch_bounds__(64 * WAVES_M * WAVES_N)
+void dd_gemm_pad0_kernel(const GemmParams p) {
+  gemm1_body<T, WAVES_M, WAVES_N, TM, TN, true, false, 0>(p);
 }
 
 // =============================================================================================
@@ -2440,6 +2456,12 @@ constexpr TileCfg kTiles[] = {
     //  2 / 4, 384x64, the GEGLU-only 160x320, three direct-conv variants, and the round-2 row-panel family.)
 };
 constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
+// tiles with a pad_lo = 0 conv instantiation (launch_tile_pad0)
+constexpr int kPad0Tiles[] = {1, 2, 3, 4, 5};
+inline bool pad0_tile(int id) {
+  for (int t : kPad0Tiles) if (t == id) return true;
+  return false;
+}
 
 inline int tile_bm(const TileCfg& t) { return t.wm * t.tm * 16; }
 inline int tile_bn(const TileCfg& t) { return t.wn * t.tn * 16; }
@@ -2612,11 +2634,17 @@ Plan make_plan(const dd_gemm_desc* d) {
   return pl;
 }
 
-template <typename T, int WM, int WN, int TM, int TN, bool CONV, bool GEGLU>
+template <typename T, int WM, int WN, int TM, int TN, bool CONV, bool GEGLU, int PAD_LO>
+constexpr auto gemm1_kernel() {
+  if constexpr (PAD_LO == 1) return dd_gemm_kernel<T, WM, WN, TM, TN, CONV, GEGLU>;
+  else return dd_gemm_pad0_kernel<T, WM, WN, TM, TN>;
+}
+
+template <typename T, int WM, int WN, int TM, int TN, bool CONV, bool GEGLU, int PAD_LO = 1>
 int launch_cfg(const GemmParams& p, const Plan& pl, hipStream_t s) {
   constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
   constexpr size_t smem = (size_t)2 * (BM + BN) * BK * sizeof(T);
-  auto kern = dd_gemm_kernel<T, WM, WN, TM, TN, CONV, GEGLU>;
+  auto kern = gemm1_kernel<T, WM, WN, TM, TN, CONV, GEGLU, PAD_LO>();
   static std::atomic<uint64_t> attr_done{0};
   dd_ensure_dyn_lds(reinterpret_cast<const void*>(kern), smem, attr_done);
   dim3 grid(pl.tiles_m * pl.tiles_n, 1, pl.split);
@@ -2758,11 +2786,31 @@ int launch_tile(const GemmParams& p, const Plan& pl, hipStream_t s) {
   return DD_ERR_UNSUPPORTED;
 }
 
+// conv with pad_lo = 0 (dd_gemm_conv_pad): the register-staged tiles only.  The LDS-DMA family keeps its one body: a
+// PAD_LO template parameter there (a shared __forceinline__ body behind two __global__ wrappers) changed the register
+// allocation of every existing dd_gemm2_kernel instantiation — its kernel-argument loads are rematerialised, not spilled,
+// only while the body IS the kernel.  make_plan reports every other tile "unsupported" for pad_lo = 0 (pad0_tile).
 template <typename T>
-int launch_dtype(const dd_gemm_desc* d, const GemmParams& p, const Plan& pl, hipStream_t s) {
+int launch_tile_pad0(const GemmParams& p, const Plan& pl, hipStream_t s) {
+  switch (kTiles[pl.tile_idx].id) {
+#if !defined(DD_DBG_ONLY_P) && !defined(DD_DBG_ONLY_C3)
+    case 1: return launch_cfg<T, 2, 2, 4, 4, true, false, 0>(p, pl, s);
+    case 2: return launch_cfg<T, 2, 2, 4, 2, true, false, 0>(p, pl, s);
+    case 3: return launch_cfg<T, 2, 2, 2, 4, true, false, 0>(p, pl, s);
+    case 4: return launch_cfg<T, 2, 2, 2, 2, true, false, 0>(p, pl, s);
+    case 5: return launch_cfg<T, 4, 2, 4, 4, true, false, 0>(p, pl, s);
+#endif
+  }
+  return DD_ERR_UNSUPPORTED;
+}
+
+template <typename T>
+int launch_dtype(const dd_gemm_desc* d, const GemmParams& p, const Plan& pl, hipStream_t s, int pad_lo) {
   int rc = DD_OK;
   if (d->phase == 2) {                      // reduce launch only (per-launch timing of a split-K GEMM)
     if (pl.split <= 1) return DD_OK;
+  } else if (pad_lo == 0) {                 // validate_pad: conv, stride 2, no upsample, no GEGLU
+    rc = launch_tile_pad0<T>(p, pl, s);
   } else if (d->epilogue == DD_EPI_GEGLU) {
     if (d->conv) return DD_ERR_UNSUPPORTED;
     rc = launch_tile<T, false, true>(p, pl, s);
@@ -2783,7 +2831,8 @@ int launch_dtype(const dd_gemm_desc* d, const GemmParams& p, const Plan& pl, hip
   return rc;
 }
 
-int validate(const dd_gemm_desc* d) {
+// pad_lo: top / left padding of a conv (dd_gemm_conv_pad); the output size is that of the (pad_lo, 1) padded image
+int validate(const dd_gemm_desc* d, int pad_lo = 1) {
   if (!d || !d->a || !d->w || !d->out) return DD_ERR_BAD_ARG;
   if (d->ln_colsum) {                                  // LayerNorm fold
     if (!d->ln_bias || d->conv || d->a2 || d->bias) return DD_ERR_BAD_ARG;
@@ -2813,7 +2862,8 @@ int validate(const dd_gemm_desc* d) {
     if (d->stride != 1 && d->stride != 2) return DD_ERR_UNSUPPORTED;
     if (d->hv <= 0 || d->wv <= 0) return DD_ERR_BAD_ARG;
     if (d->rows % (d->hout * d->wout) != 0) return DD_ERR_BAD_ARG;
-    if ((d->hv + 2 - 3) / d->stride + 1 != d->hout || (d->wv + 2 - 3) / d->stride + 1 != d->wout) return DD_ERR_BAD_ARG;
+    if ((d->hv + pad_lo + 1 - 3) / d->stride + 1 != d->hout || (d->wv + pad_lo + 1 - 3) / d->stride + 1 != d->wout)
+      return DD_ERR_BAD_ARG;
   } else {
     if (d->lda & 7) return DD_ERR_BAD_ARG;
     if (d->a2) {
@@ -2833,6 +2883,23 @@ int validate(const dd_gemm_desc* d) {
   return DD_OK;
 }
 
+// pad_lo = 0 exists for one layer: Downsample2D(padding=0) — conv, stride 2, no upsample, plain or SiLU epilogue.
+// hout = (hin - 2) / 2 + 1 needs hin >= 2 (a 1-pixel image padded to 2 has no 3x3 window).
+int validate_pad(const dd_gemm_desc* d, int pad_lo) {
+  if (pad_lo != 0 && pad_lo != 1) return DD_ERR_BAD_ARG;
+  if (pad_lo == 1) return validate(d);
+  if (!d || !d->conv) return DD_ERR_BAD_ARG;
+  if (d->stride != 2 || d->hv != d->hin || d->wv != d->win || d->epilogue == DD_EPI_GEGLU) return DD_ERR_UNSUPPORTED;
+  if (d->hin < 2 || d->win < 2) return DD_ERR_BAD_ARG;
+  return validate(d, 0);
+}
+
+Plan make_plan_pad(const dd_gemm_desc* d, int pad_lo) {
+  Plan pl = make_plan(d);
+  if (pad_lo == 0 && !pl.unsupported && !pad0_tile(kTiles[pl.tile_idx].id)) pl.unsupported = true;
+  return pl;
+}
+
 thread_local char g_kname[160];
 
 }  // namespace
@@ -2845,18 +2912,26 @@ extern "C" int dd_gemm_tile_id(int index) { return (index >= 0 && index < kNumTi
 // step); the slab offset is kept because dd_groupnorm_splitk's callers address the slabs behind it.
 constexpr int64_t DD_COUNTER_BYTES = 65536;
 
-extern "C" int64_t dd_gemm_workspace_bytes(const dd_gemm_desc* d) {
-  if (validate(d) != DD_OK) return 0;
-  const Plan pl = make_plan(d);
+namespace {
+
+int64_t workspace_bytes(const dd_gemm_desc* d, int pad_lo) {
+  if (validate_pad(d, pad_lo) != DD_OK) return 0;
+  const Plan pl = make_plan_pad(d, pad_lo);
   if (pl.unsupported || pl.split <= 1) return 0;
   return DD_COUNTER_BYTES + (int64_t)pl.split * d->rows * d->n * (int64_t)sizeof(float);
 }
 
-extern "C" const char* dd_gemm_kernel_name(const dd_gemm_desc* d) {
-  if (validate(d) != DD_OK) return "invalid";
-  const Plan pl = make_plan(d);
+const char* kernel_name(const dd_gemm_desc* d, int pad_lo) {
+  const int vc = validate_pad(d, pad_lo);
+  if (vc != DD_OK) return (pad_lo == 0 && vc == DD_ERR_UNSUPPORTED) ? "unsupported" : "invalid";
+  const Plan pl = make_plan_pad(d, pad_lo);
   if (pl.unsupported) return "unsupported";
   const TileCfg& t = kTiles[pl.tile_idx];
+  if (pad_lo == 0) {                                   // launch_tile_pad0: dd_gemm_pad0_kernel
+    snprintf(g_kname, sizeof(g_kname), "dd_gemm_pad0_kernel<%s, %d, %d, %d, %d> split=%d grid=%dx%d tile=%s",
+             d->dtype == DD_F16 ? "_Float16" : "__bf16", t.wm, t.wn, t.tm, t.tn, pl.split, pl.tiles_m, pl.tiles_n, t.name);
+    return g_kname;
+  }
   if (t.stages < 0) {
     const bool band = t.stages == -3;
     const int nsw = (t.id == 31 || band) ? 5 : (t.id >= 37 ? 6 : (t.id >= 35 ? 3 : 4));
@@ -2881,10 +2956,10 @@ extern "C" const char* dd_gemm_kernel_name(const dd_gemm_desc* d) {
   return g_kname;
 }
 
-extern "C" int dd_gemm(const dd_gemm_desc* d, dd_stream_t stream) {
-  const int vc = validate(d);
+int gemm_run(const dd_gemm_desc* d, int pad_lo, dd_stream_t stream) {
+  const int vc = validate_pad(d, pad_lo);
   if (vc != DD_OK) return vc;
-  const Plan pl = make_plan(d);
+  const Plan pl = make_plan_pad(d, pad_lo);
   if (pl.unsupported) return DD_ERR_UNSUPPORTED;
   GemmParams p{};
   p.g_per_tile = pl.g_per_tile; p.chunks_per_split = pl.chunks_per_split;
@@ -2947,6 +3022,22 @@ extern "C" int dd_gemm(const dd_gemm_desc* d, dd_stream_t stream) {
   }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
-  if (d->dtype == DD_F16) return launch_dtype<_Float16>(d, p, pl, s);
-  return launch_dtype<__bf16>(d, p, pl, s);
+  if (d->dtype == DD_F16) return launch_dtype<_Float16>(d, p, pl, s, pad_lo);
+  return launch_dtype<__bf16>(d, p, pl, s, pad_lo);
+}
+
+}  // namespace
+
+extern "C" int64_t dd_gemm_workspace_bytes(const dd_gemm_desc* d) { return workspace_bytes(d, 1); }
+extern "C" const char* dd_gemm_kernel_name(const dd_gemm_desc* d) { return kernel_name(d, 1); }
+extern "C" int dd_gemm(const dd_gemm_desc* d, dd_stream_t stream) { return gemm_run(d, 1, stream); }
+
+extern "C" int dd_gemm_conv_pad(const dd_gemm_desc* d, int32_t pad_lo, dd_stream_t stream) {
+  return gemm_run(d, pad_lo, stream);
+}
+extern "C" int64_t dd_gemm_conv_pad_workspace_bytes(const dd_gemm_desc* d, int32_t pad_lo) {
+  return workspace_bytes(d, pad_lo);
+}
+extern "C" const char* dd_gemm_conv_pad_kernel_name(const dd_gemm_desc* d, int32_t pad_lo) {
+  return kernel_name(d, pad_lo);
 }

@@ -203,7 +203,8 @@ def _flush_and_warm(device, warm):
             t.sum()
 
 
-def _autotune(lib, d, key, out_shape, dtype, device, warm=()):
+def _autotune(lib, d, key, out_shape, dtype, device, warm=(), pad_lo=1):
+    """pad_lo: the conv's top / left padding; 0 times the dd_gemm_conv_pad launches conv3x3(pad=0) will make."""
     _load_default_table()
     hit = _TUNED.get(key)
     challenge = ()
@@ -220,20 +221,28 @@ def _autotune(lib, d, key, out_shape, dtype, device, warm=()):
     d.out, d.ldc, d.accumulate = scratch.data_ptr(), scratch.stride(0), 0
     best, best_t = (0, 0, 0), float("inf")
     stream = _stream()
+    if pad_lo == 1:
+        launch, ws_bytes = lib.dd_gemm, lib.dd_gemm_workspace_bytes
+    else:
+        def launch(dp, st):
+            return lib.dd_gemm_conv_pad(dp, pad_lo, st)
+
+        def ws_bytes(dp):
+            return lib.dd_gemm_conv_pad_workspace_bytes(dp, pad_lo)
 
     def timed(tile, split, iters, ink=0):          # ink: third entry of a table row (split-K form), always 0 since round 5
         d.tile, d.split_k = tile, split
-        need = lib.dd_gemm_workspace_bytes(ctypes.byref(d))
+        need = ws_bytes(ctypes.byref(d))
         if need > 0:
             ws = workspace(need, device)
             d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * 4
-        if lib.dd_gemm(ctypes.byref(d), stream) != 0:
+        if launch(ctypes.byref(d), stream) != 0:
             return None
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         if not _COLD:
             e0.record()
             for _ in range(iters):
-                lib.dd_gemm(ctypes.byref(d), stream)
+                launch(ctypes.byref(d), stream)
             e1.record()
             e1.synchronize()
             return e0.elapsed_time(e1) / iters
@@ -241,7 +250,7 @@ def _autotune(lib, d, key, out_shape, dtype, device, warm=()):
         for _ in range(iters):
             _flush_and_warm(device, warm)
             e0.record()
-            lib.dd_gemm(ctypes.byref(d), stream)
+            launch(ctypes.byref(d), stream)
             e1.record()
             e1.synchronize()
             samples.append(e0.elapsed_time(e1))
@@ -588,8 +597,11 @@ def thin_conv_ok(cin, cout, stride, m):
 
 
 def conv3x3(x, w, bias, m, hin, win, *, stride=1, up_size=None, rowvec=None, res=None,
-            alpha=1.0, out=None, accumulate=False, epilogue=DD_EPI_NONE, tile=0, split_k=0, gn_next=None):
+            alpha=1.0, out=None, accumulate=False, epilogue=DD_EPI_NONE, tile=0, split_k=0, gn_next=None, pad=1):
     """3x3 / pad 1 convolution as an implicit GEMM on an NHWC batch.
+
+    pad=0 (stride 2, no upsample): diffusers' Downsample2D(padding=0) — F.pad(x, (0, 1, 0, 1)) then a 3x3 / stride 2 /
+    pad 0 conv, hout = (hin - 2) // 2 + 1 — launched through dd_gemm_conv_pad with its own tuning key.
 
     gn_next = (GroupNorm module, silu, want_x): the GroupNorm that reads this conv's output next.  When the conv runs
     split-K (two launches) and the image takes the single-launch GroupNorm, the REDUCE launch is replaced by
@@ -606,8 +618,12 @@ def conv3x3(x, w, bias, m, hin, win, *, stride=1, up_size=None, rowvec=None, res
     if not x.is_contiguous() or x.shape[0] != m * hin * win:
         raise ValueError("conv input must be contiguous (m*h*w, cin)")
     hv, wv = (hin, win) if up_size is None else (int(up_size[0]), int(up_size[1]))
-    hout = (hv + 2 - 3) // stride + 1
-    wout = (wv + 2 - 3) // stride + 1
+    if pad not in (0, 1):
+        raise ValueError("conv3x3: pad is 1 (nn.Conv2d(padding=1)) or 0 (Downsample2D(padding=0))")
+    if pad == 0 and (stride != 2 or up_size is not None or hin < 2 or win < 2):
+        raise ValueError("conv3x3(pad=0) is the stride-2 downsample of an image of at least 2 x 2 pixels, without upsample")
+    hout = (hv + pad + 1 - 3) // stride + 1
+    wout = (wv + pad + 1 - 3) // stride + 1
     cout = w.shape[0]
     if w.shape[1] != 9 * cin or not w.is_contiguous():
         raise ValueError("conv weight must be contiguous [cout, 9*cin]")
@@ -616,7 +632,7 @@ def conv3x3(x, w, bias, m, hin, win, *, stride=1, up_size=None, rowvec=None, res
         out = torch.empty((rows, cout), dtype=x.dtype, device=x.device)
     else:
         _forget_derived(out)
-    if thin_conv_ok(cin, cout, stride, m) and up_size is None and rowvec is None and res is None and alpha == 1.0 \
+    if pad == 1 and thin_conv_ok(cin, cout, stride, m) and up_size is None and rowvec is None and res is None and alpha == 1.0 \
             and not accumulate and epilogue in (DD_EPI_NONE, DD_EPI_SILU) and tile == 0 and split_k == 0 \
             and out.is_contiguous():
         # thin channel counts on a large image (the condition embedder's first layers): patch-in-LDS direct conv
@@ -646,6 +662,8 @@ def conv3x3(x, w, bias, m, hin, win, *, stride=1, up_size=None, rowvec=None, res
     d.hin, d.win, d.cin, d.hv, d.wv = hin, win, cin, hv, wv
     d.hout, d.wout, d.stride = hout, wout, stride
     d.dtype = _dt(x); d.tile = tile; d.split_k = split_k
+    if pad == 0:
+        return _conv3x3_pad0(lib, d, x, res, out, m, rows, cout, cin, w)
     if tile == 0 and split_k == 0:
         d.tile, d.split_k, _ = _autotune(lib, d, ("c", m, hin, win, cin, cout, stride, hv, wv, d.dtype),
                                       (rows, cout), x.dtype, x.device, warm=(x, res))
@@ -688,6 +706,43 @@ def conv3x3(x, w, bias, m, hin, win, *, stride=1, up_size=None, rowvec=None, res
         return out
     _native.check(lib.dd_gemm(ctypes.byref(d), _stream()), "conv3x3")
     return out
+
+
+def _conv3x3_pad0(lib, d, x, res, out, m, rows, cout, cin, w):
+    """conv3x3(pad=0): tuned under its own key (the pad-1 keys are untouched), launched through dd_gemm_conv_pad."""
+    if d.tile == 0 and d.split_k == 0:
+        d.tile, d.split_k, _ = _autotune(lib, d, ("c", m, d.hin, d.win, cin, cout, d.stride, d.hv, d.wv, d.dtype, "p0"),
+                                      (rows, cout), x.dtype, x.device, warm=(x, res), pad_lo=0)
+    need = lib.dd_gemm_conv_pad_workspace_bytes(ctypes.byref(d), 0)
+    if need > 0 or _DBG_STAMP_WS:
+        ws = workspace(need, x.device)
+        d.ws = ws.data_ptr(); d.ws_bytes = ws.numel() * 4
+    e0 = _TIMER.start() if _TIMER is not None else None
+    _native.check(lib.dd_gemm_conv_pad(ctypes.byref(d), 0, _stream()), "conv3x3(pad=0)")
+    if e0 is not None:
+        name = lib.dd_gemm_conv_pad_kernel_name(ctypes.byref(d), 0).decode().split(" split=")[0]
+        _TIMER.stop(e0, name + (" conv %dx%dx%d" % (rows, cout, 9 * cin) if _TIMER.shapes else ""), 2.0 * rows * cout * 9 * cin,
+                    2.0 * (x.numel() + w.numel() + rows * cout * (1 + (1 if d.res else 0) + (1 if d.accumulate else 0))))
+    return out
+
+
+def vae_posterior(moments, wq, bq, m, h, w, noise=None, scale=1.0, out_f32=False):
+    """quant_conv + DiagonalGaussianDistribution of the VAE encoder (dd_vae_posterior): moments (m*h*w, 8) NHWC rows in
+    T, wq (8, 8) / bq (8,) fp32, noise (m, 4, h, w) in T or None (mode).  Returns scale * z as (m, 4, h, w), fp32 when
+    out_f32 else T."""
+    lib = _native.load()
+    _need_gpu(moments, wq, bq, noise)
+    if moments.shape != (m * h * w, 8) or not moments.is_contiguous():
+        raise ValueError("moments must be contiguous (m*h*w, 8), got %s" % (tuple(moments.shape),))
+    if wq.dtype != torch.float32 or bq.dtype != torch.float32 or wq.numel() != 64 or bq.numel() != 8 \
+            or not wq.is_contiguous() or not bq.is_contiguous():
+        raise ValueError("quant_conv weight / bias must be contiguous fp32 (8, 8) / (8,)")
+    if noise is not None and (noise.shape != (m, 4, h, w) or noise.dtype != moments.dtype or not noise.is_contiguous()):
+        raise ValueError("noise must be a contiguous %s (%d, 4, %d, %d) tensor" % (moments.dtype, m, h, w))
+    z = torch.empty((m, 4, h, w), dtype=torch.float32 if out_f32 else moments.dtype, device=moments.device)
+    _native.check(lib.dd_vae_posterior(_ptr(moments), _ptr(wq), _ptr(bq), _ptr(noise), _ptr(z), m, h, w, float(scale),
+                                       int(bool(out_f32)), _dt(moments), _stream()), "vae_posterior")
+    return z
 
 
 def groupnorm(x, gamma, beta, m, hw, groups, eps, silu, x2=None, out=None):

@@ -177,6 +177,20 @@ int dd_gemm_tile_id(int index);
 /* Name of the kernel symbol dd_gemm would launch for `d` (for profile matching). */
 const char* dd_gemm_kernel_name(const dd_gemm_desc* d);
 
+/* conv3x3 with a chosen top / left zero padding pad_lo: output pixel o reads input rows and columns
+ * o*stride - pad_lo + 0..2; reads past the bottom / right edge of the stored image are zero, as in every conv.
+ *   pad_lo = 1: exactly dd_gemm / dd_gemm_workspace_bytes / dd_gemm_kernel_name (same plan, kernel and bits).
+ *   pad_lo = 0: diffusers' Downsample2D(padding=0) of the VAE encoder's down blocks,
+ *               F.pad(x, (0, 1, 0, 1)) followed by nn.Conv2d(c, c, 3, stride=2, padding=0)
+ *               (AutoencoderKL.encode, runner/base_runner.py:469-475).  conv = 1, stride = 2, hv == hin, wv == win,
+ *               hin, win >= 2, hout = (hin - 2) / 2 + 1, wout = (win - 2) / 2 + 1, no GEGLU; else DD_ERR_UNSUPPORTED or
+ *               DD_ERR_BAD_ARG.  Only the register-staged tiles (ids 1-5, dd_gemm_pad0_kernel) have the kernel; any
+ *               other tile is DD_ERR_UNSUPPORTED ("unsupported" from the name query), so the LDS-DMA, direct small-image
+ *               and pipelined families and the thin conv never take it. */
+int dd_gemm_conv_pad(const dd_gemm_desc* d, int32_t pad_lo, dd_stream_t stream);
+int64_t dd_gemm_conv_pad_workspace_bytes(const dd_gemm_desc* d, int32_t pad_lo);
+const char* dd_gemm_conv_pad_kernel_name(const dd_gemm_desc* d, int32_t pad_lo);
+
 /* ------------------------------------------------------------------------- *
  * GroupNorm (+ optional SiLU), NHWC, optional channel-concat of two sources.
  *   y[m, p, c] = act( (x[m,p,c] - mean[m,g]) * rstd[m,g] * gamma[c] + beta[c] )
@@ -403,6 +417,17 @@ int dd_softmax_rows(const float* s, void* p, int64_t rows, int32_t cols, int64_t
 int dd_conv3x3_small_cout(const void* x, const void* w, const void* bias, void* y_nchw,
                           int32_t m, int32_t h, int32_t wd, int32_t cin, int32_t cout,
                           int32_t dtype, dd_stream_t stream);
+
+/* VAE encoder posterior (diffusers AutoencoderKL.encode -> DiagonalGaussianDistribution, scaled as the reference's
+ * runner/base_runner.py:469-475 does): per latent pixel, in fp32,
+ *   p = wq x + bq                      quant_conv (1x1, 8 -> 8); x = the 8 channels conv_out wrote
+ *   mean = p[0:4], logvar = clamp(p[4:8], -30, 20)
+ *   z = mean + exp(0.5 logvar) * noise, or z = mean when noise == NULL (mode())
+ *   out = scale * z
+ * moments: T NHWC rows (m * h * w, 8), 16-byte aligned; wq: fp32 [8][8] (out, in); bq: fp32 [8];
+ * noise: T NCHW (m, 4, h, w) or NULL; z: NCHW (m, 4, h, w), fp32 when out_f32 else T. */
+int dd_vae_posterior(const void* moments, const float* wq, const float* bq, const void* noise, void* z,
+                     int32_t m, int32_t h, int32_t w, float scale, int32_t out_f32, int32_t dtype, dd_stream_t stream);
 
 /* conv3x3 / pad 1 / stride 1 or 2 for THIN channel counts on large NHWC images — the first layers of
  * ControlNetConditioningEmbedding (networks/map_embedder.py:79-113: 3 -> 16 -> 16 -> 32 -> 32 channels on 224x400 ..
