@@ -14,7 +14,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "lib", "obj")
 LIBNAME = "libdualdiff_hip.so"
-SOURCES = ["gemm.hip", "norm.hip", "attention.hip", "elementwise.hip", "xattn.hip", "gemm8.hip", "tokens.hip", "vae.hip"]
+SOURCES = ["gemm.hip", "norm.hip", "attention.hip", "elementwise.hip", "xattn.hip", "gemm8.hip", "tokens.hip", "vae.hip",
+           "clip.hip"]
 # per-source extra flags: the attention softmax lives on the MFMA results, so ask LLVM for the
 # VGPR-destination form of MFMA (gfx950 has a unified register file) instead of AGPR accumulators
 # that cost a v_accvgpr_read/write per touched element.
@@ -22,7 +23,9 @@ EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-hon
                # round 5: the same form for the GEMM / conv kernels — four-wave kernels with a 512-register budget otherwise get
                # AGPR accumulators (and, in dd_gemm3's rotating schedule, v_accvgpr shuffles per K-step).  Same-box A/B, three
                # alternating rounds: fp16 87.32 -> 87.34, bf16 89.80 -> 89.97, 4 scenes batched 112.7 -> 113.4 (+0.6 %)
-               "gemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+               "gemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               # the causal softmax reads its whole score strip out of the MFMA results, as attention.hip's does
+               "clip.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 ARCH = "gfx950"
 
 

@@ -150,6 +150,11 @@ SIGNATURES = {
                                         c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "dd_vae_posterior": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float,
                                    c_int32, c_int32, c_void_p]),
+    "dd_clip_embed": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                c_int32, c_int32, c_void_p]),
+    "dd_causal_attention": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                      c_int64, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_float,
+                                      c_int32, c_void_p]),
     "dd_conv3x3_thin": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                   c_int32, c_int32, c_int32, c_void_p]),
     "dd_cfg_ddim_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,

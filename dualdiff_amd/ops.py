@@ -884,6 +884,59 @@ def attention(q, k, v, batch, lq, lk, heads, head_dim, scale=None, *, kv_batch_m
     return out
 
 
+CAUSAL_ATTN_MAX_L = 128         # DD_CAUSAL_ATTN_MAX_L of include/dualdiff_hip.h
+
+
+def causal_attention(q, k, v, batch, l, heads, head_dim, out=None):
+    """softmax_{j <= i}(head_dim^-0.5 * q_i . k_j) v_j per (sequence, head) — CLIP's self-attention (dd_causal_attention:
+    head_dim 64, l <= CAUSAL_ATTN_MAX_L).  q, k, v: (batch*l, >= heads*head_dim) row-strided views, so the column slices
+    of a fused Q|K|V projection are passed without copies; returns (batch*l, heads*head_dim)."""
+    lib = _native.load()
+    _need_gpu(q, k, v, out)
+    q, k, v = _rows2d(q), _rows2d(k), _rows2d(v)
+    for t in (q, k, v):
+        if t.shape[0] != batch * l or t.shape[1] < heads * head_dim or t.dtype != q.dtype:
+            raise ValueError("causal_attention operands must be (%d, >= %d) %s views, got %s %s"
+                             % (batch * l, heads * head_dim, q.dtype, tuple(t.shape), t.dtype))
+    if out is None:
+        out = torch.empty((batch * l, heads * head_dim), dtype=q.dtype, device=q.device)
+    elif out.shape[0] != batch * l or out.shape[1] < heads * head_dim or out.dtype != q.dtype:
+        raise ValueError("causal_attention: out must be (%d, >= %d) %s" % (batch * l, heads * head_dim, q.dtype))
+    else:
+        _forget_derived(out)
+    out = _rows2d(out)
+    e0 = _TIMER.start() if _TIMER is not None else None
+    rc = lib.dd_causal_attention(_ptr(q), _ptr(k), _ptr(v), _ptr(out), q.stride(0), k.stride(0), v.stride(0),
+                                 out.stride(0), l * q.stride(0), l * k.stride(0), l * v.stride(0), l * out.stride(0),
+                                 batch, l, heads, head_dim, float(head_dim) ** -0.5, _dt(q), _stream())
+    _native.check(rc, "causal_attention")
+    if e0 is not None:
+        _TIMER.stop(e0, "dd_causal_attn_kernel<%s>" % ("f16" if q.dtype == torch.float16 else "bf16"),
+                    2.0 * batch * heads * l * l * head_dim, 2.0 * heads * head_dim * batch * l * 4)
+    return out
+
+
+def clip_embed(ids, tok, pos, eos_token_id):
+    """CLIPTextEmbeddings + the pooling position (dd_clip_embed): ids (b, l) int64 on the GPU, tok (vocab, c), pos
+    (>= l, c) -> (rows (b*l, c) = tok[ids] + pos[:l] summed in fp32 and rounded once, pool_index (b,) int32 = the
+    position pooler_output reads: ids.argmax(-1) for eos_token_id == 2, else the first eos_token_id, 0 when absent).
+    Ids outside [0, vocab) are clamped by the kernel."""
+    lib = _native.load()
+    _need_gpu(ids, tok, pos)
+    if ids.dim() != 2 or ids.dtype != torch.int64 or not ids.is_contiguous():
+        raise ValueError("ids must be a contiguous (b, l) int64 tensor, got %s %s" % (tuple(ids.shape), ids.dtype))
+    b, l = ids.shape
+    if tok.dim() != 2 or pos.dim() != 2 or tok.shape[1] != pos.shape[1] or pos.shape[0] < l or tok.dtype != pos.dtype \
+            or not tok.is_contiguous() or not pos.is_contiguous():
+        raise ValueError("token / position tables must be contiguous (vocab, c) / (>= %d, c) of one dtype" % l)
+    rows = torch.empty((b * l, tok.shape[1]), dtype=tok.dtype, device=tok.device)
+    pool = torch.empty((b,), dtype=torch.int32, device=tok.device)
+    rc = lib.dd_clip_embed(_ptr(ids), _ptr(tok), _ptr(pos), _ptr(rows), _ptr(pool), b, l, tok.shape[1], tok.shape[0],
+                           int(eos_token_id), _dt(tok), _stream())
+    _native.check(rc, "clip_embed")
+    return rows, pool
+
+
 _ZERO_BIAS = {}
 
 

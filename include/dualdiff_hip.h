@@ -429,6 +429,40 @@ int dd_conv3x3_small_cout(const void* x, const void* w, const void* bias, void* 
 int dd_vae_posterior(const void* moments, const float* wq, const float* bq, const void* noise, void* z,
                      int32_t m, int32_t h, int32_t w, float scale, int32_t out_f32, int32_t dtype, dd_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ * CLIP text encoder (csrc/clip.hip): the SD-v1.5 `text_encoder` (transformers.CLIPTextModel) that the reference calls at
+ * runner/base_runner.py:119,511-514, runner/multiview_runner.py:145,427-428 (`text_encoder(ids)[0]`), through diffusers'
+ * _encode_prompt at pipeline/pipeline_bev_controlnet.py:273 and at networks/bbox_embedder.py:133-145
+ * (`text_encoder(ids).pooler_output[0]`).  Its Linear / LayerNorm layers run on dd_gemm / dd_layernorm; these two entry
+ * points are the rest.
+ * ------------------------------------------------------------------------- */
+/* CLIPTextEmbeddings + the pooling position of CLIPTextTransformer, one launch:
+ *   out[b * l + t, :] = T( float(tok[clamp(ids[b, t], 0, vocab - 1)]) + float(pos[t]) )      (one rounding)
+ *   pool_index[b]     = eos_token_id == 2 ? first position of the largest id of sequence b   (ids[b].argmax())
+ *                                         : first position with ids[b, t] == eos_token_id, 0 when there is none
+ * — the row of sequence b that pooler_output reads, left in device memory so that pooling needs no host synchronisation.
+ * ids: int64 [batch * l] (device); tok [vocab][c], pos [>= l][c], out [batch * l][c] in `dtype`; pool_index int32 [batch].
+ * c % 8 == 0, tok / pos / out 16-byte aligned (rows move as 16-byte vectors), else DD_ERR_BAD_ARG.  Ids outside
+ * [0, vocab) are clamped for the gather (nothing is read outside the table); the pooling rule sees them as they are. */
+int dd_clip_embed(const int64_t* ids, const void* tok, const void* pos, void* out, int32_t* pool_index,
+                  int32_t batch, int32_t l, int32_t c, int32_t vocab, int32_t eos_token_id, int32_t dtype,
+                  dd_stream_t stream);
+
+/* Causal self-attention (CLIPAttention with the causal mask only — SD-v1.5's config has no use_attention_mask, padding
+ * tokens attend like any other position):
+ *   O[b, i, h, :] = softmax_{j <= i}( scale * Q[b,i,h,:].K[b,j,h,:] ) V[b,j,h,:]
+ * Q / K / V / O: element (b, i, h, d) at  base + b * batch_stride + i * ld + h * head_dim + d  (elements), so Q, K, V may
+ * be column slices of one fused [batch * l][3 * heads * head_dim] projection.  head_dim == 64 and
+ * 1 <= l <= DD_CAUSAL_ATTN_MAX_L, else DD_ERR_UNSUPPORTED; NULL / misaligned (16 bytes; ld and batch strides multiples of
+ * 8) / non-positive arguments are DD_ERR_BAD_ARG; both are decided before anything is launched.  Numerics as dd_attention:
+ * fp32 scores and softmax (exp2 with scale * log2 e), probabilities rounded to `dtype` before P.V, fp32 accumulation, one
+ * rounding at the store; a masked key's probability is exactly 0. */
+#define DD_CAUSAL_ATTN_MAX_L 128
+int dd_causal_attention(const void* q, const void* k, const void* v, void* o, int64_t ldq, int64_t ldk, int64_t ldv,
+                        int64_t ldo, int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride,
+                        int64_t o_batch_stride, int32_t batch, int32_t l, int32_t heads, int32_t head_dim, float scale,
+                        int32_t dtype, dd_stream_t stream);
+
 /* conv3x3 / pad 1 / stride 1 or 2 for THIN channel counts on large NHWC images — the first layers of
  * ControlNetConditioningEmbedding (networks/map_embedder.py:79-113: 3 -> 16 -> 16 -> 32 -> 32 channels on 224x400 ..
  * 112x200).  x (m, hin, win, cin), w [cout][9*cin] (k = tap * cin + channel), bias [cout] or NULL,
