@@ -500,14 +500,15 @@ def test_attention_ragged_tail_all_scores_negative(ops, variant, lk):
     below 0 the padded keys would own the running max (and, without the zeroed ones column, the
     denominator): the result must still be the softmax over the lk real keys only."""
     b, lq, h, d = 2, 48, 8, 40
-    dtype = torch.bfloat16
-    q = rnd((b * lq, h * d), dtype, 1) + 1.5
-    k = -(rnd((b * lk, h * d), dtype, 2).abs() + 1.0) * 2.0       # q . k strongly negative everywhere
-    v = rnd((b * lk, h * d), dtype, 3)
-    y = ops.attention(q, k, v, b, lq, lk, h, d, variant=variant)
-    ref = L.attention_ref(q, k, v, b, lq, lk, h, d)
-    assert torch.isfinite(y.float()).all()
-    check(y, ref, dtype, "attention ragged tail lk=%d v%d" % (lk, variant), 4.0)
+    # bf16 and fp16: a padded key's exp2(0 - m_run) reaches 2^49 here, which bf16 holds and fp16 turns into inf
+    for dtype in (torch.bfloat16, torch.float16):
+        q = rnd((b * lq, h * d), dtype, 1) + 1.5
+        k = -(rnd((b * lk, h * d), dtype, 2).abs() + 1.0) * 2.0       # q . k strongly negative everywhere
+        v = rnd((b * lk, h * d), dtype, 3)
+        y = ops.attention(q, k, v, b, lq, lk, h, d, variant=variant)
+        ref = L.attention_ref(q, k, v, b, lq, lk, h, d)
+        assert torch.isfinite(y.float()).all()
+        check(y, ref, dtype, "attention ragged tail lk=%d v%d %s" % (lk, variant, dtype), 4.0)
 
 
 @pytest.mark.parametrize("variant", [0])
@@ -572,22 +573,23 @@ def test_attention_prescaled_q(ops, variant, kind, lk):
     spikes (rescale branch, also inside the ragged last chunk), rows whose every score is far below zero
     (the first chunk must LOWER the initial max of 0; padded keys score above every real one), plain data."""
     b, lq, h, d = 2, 80, 8, 40
-    dtype = torch.bfloat16
-    q = rnd((b * lq, h * d), dtype, 1)
-    k = rnd((b * lk, h * d), dtype, 2)
-    v = rnd((b * lk, h * d), dtype, 3)
-    if kind == "spike":
-        k[lk - 1] = q[7] * 6.0
-        if lk > 40:
-            k[lk // 2] = q[9] * 4.0
-    elif kind == "negative":
-        q = q + 1.5
-        k = -(k.abs() + 1.0) * 3.0
-    # q is what the projection epilogue would have stored: already in log2 units
-    y = ops.attention(q, k, v, b, lq, lk, h, d, variant=variant, q_prescaled=True)
-    ref = L.attention_ref(q, k, v, b, lq, lk, h, d, scale=LN2)
-    assert torch.isfinite(y.float()).all()
-    check(y, ref, dtype, "prescaled attention %s lk=%d v%d" % (kind, lk, variant), 4.0)
+    # the "negative" and "spike" kinds also in fp16: the type in which a padded key's probability overflows
+    for dtype in ((torch.bfloat16,) if kind == "plain" else (torch.bfloat16, torch.float16)):
+        q = rnd((b * lq, h * d), dtype, 1)
+        k = rnd((b * lk, h * d), dtype, 2)
+        v = rnd((b * lk, h * d), dtype, 3)
+        if kind == "spike":
+            k[lk - 1] = q[7] * 6.0
+            if lk > 40:
+                k[lk // 2] = q[9] * 4.0
+        elif kind == "negative":
+            q = q + 1.5
+            k = -(k.abs() + 1.0) * 3.0
+        # q is what the projection epilogue would have stored: already in log2 units
+        y = ops.attention(q, k, v, b, lq, lk, h, d, variant=variant, q_prescaled=True)
+        ref = L.attention_ref(q, k, v, b, lq, lk, h, d, scale=LN2)
+        assert torch.isfinite(y.float()).all()
+        check(y, ref, dtype, "prescaled attention %s lk=%d v%d %s" % (kind, lk, variant, dtype), 4.0)
 
 
 @pytest.mark.parametrize("variant", [0])
