@@ -14,8 +14,12 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "lib", "obj")
 LIBNAME = "libdualdiff_hip.so"
-SOURCES = ["gemm.hip", "norm.hip", "attention.hip", "elementwise.hip", "xattn.hip", "gemm8.hip", "tokens.hip", "vae.hip",
-           "clip.hip"]
+# The GEMM / conv kernel families are one translation unit each, dd_gemm2_kernel one per form (csrc/gemm_device.h).
+GEMM_SOURCES = ["gemm23.hip", "gemm2_conv.hip", "gemm1.hip", "conv3s.hip", "gemm2_geglu.hip", "gemm4.hip", "gemm.hip"]
+# Longest compile first, so that the pool does not end on one long unit: gemm23 30 s, gemm2_conv and attention 20 s, gemm1
+# and conv3s 16 s, every other one under 10 s.
+SOURCES = ["gemm23.hip", "gemm2_conv.hip", "attention.hip", "gemm1.hip", "conv3s.hip", "gemm2_geglu.hip", "gemm4.hip",
+           "norm.hip", "elementwise.hip", "tokens.hip", "xattn.hip", "clip.hip", "gemm8.hip", "vae.hip", "gemm.hip"]
 # per-source extra flags: the attention softmax lives on the MFMA results, so ask LLVM for the
 # VGPR-destination form of MFMA (gfx950 has a unified register file) instead of AGPR accumulators
 # that cost a v_accvgpr_read/write per touched element.
@@ -23,7 +27,7 @@ EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-hon
                # round 5: the same form for the GEMM / conv kernels — four-wave kernels with a 512-register budget otherwise get
                # AGPR accumulators (and, in dd_gemm3's rotating schedule, v_accvgpr shuffles per K-step).  Same-box A/B, three
                # alternating rounds: fp16 87.32 -> 87.34, bf16 89.80 -> 89.97, 4 scenes batched 112.7 -> 113.4 (+0.6 %)
-               "gemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               **{src: ["-mllvm", "-amdgpu-mfma-vgpr-form=1"] for src in GEMM_SOURCES},
                # the causal softmax reads its whole score strip out of the MFMA results, as attention.hip's does
                "clip.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 ARCH = "gfx950"

@@ -3,7 +3,8 @@
 // None of these macros is defined in the product build (dualdiff_amd/_build.py passes no -DDD_DBG_*; bench.py lists every
 // DD_* environment variable of a run in its line): each flag below is then `false`, each hook expands to nothing, and the
 // kernels compile to the same ISA as before this header existed (checked byte for byte when it was introduced).  The
-// diagnostic libraries are built by tools/build_dbg_libs.sh, tools/gemm4_bound.sh and tools/conv3s_bound.sh, loaded with
+// diagnostic libraries are built by tools/build_dbg_libs.sh, tools/gemm4_bound.sh and tools/conv3s_bound.sh (each compiles only
+// the translation units of the kernel family it asks about and links the product objects of the rest), loaded with
 // DD_HIP_LIB=... (which bench.py refuses without --allow-alt-lib), and exist to answer ONE question each: which side of a
 // loop sets its length.  Their results are garbage where noted; they are timing instruments, not code paths.
 //
@@ -20,7 +21,6 @@
 //   DD_DBG_C3_NOMFMA / _NOGATHER / _NOWREAD / _NOBAR / _NOWAIT / _NODMA      dd_conv3s: one side of the (chunk, tap) step
 //   DD_DBG_NOEXP / _NOSTAGE dd_attn5               the softmax exponentials become moves / no K, V staging (tiles hold garbage)
 //   DD_DBG_STAMP           dd_gemm2/3, conv3s      s_memtime stamps at phase boundaries into the last MiB of the workspace
-//   DD_DBG_ONLY_P / _C3    host dispatch           a quick-to-compile library with one kernel family (reading its ISA)
 #pragma once
 #include <stdint.h>
 

@@ -10,7 +10,7 @@
 // bytes and by LDS fragment reads; fp8 halves both per multiply-accumulate, and
 // v_mfma_scale_f32_16x16x128_f8f6f4 (unit block scales: a plain fp8 16x16x128) retires 4x the K of the 16-bit 16x16x32 in 2x
 // its cycles.  128 x 128 tile, 4 waves of 64 x 64, K steps of 128 BYTES (= 128 fp8 values: the same 128-B LDS rows, 16-B
-// XOR swizzle and LDS-DMA staging as csrc/gemm.hip), 2 slots and two workgroups per CU; per K step a wave issues 16 MFMAs
+// XOR swizzle and LDS-DMA staging as csrc/gemm2_kernel.h), 2 slots and two workgroups per CU; per K step a wave issues 16 MFMAs
 // against 16 ds_read_b128.
 // The operand k order inside an MFMA is irrelevant as long as A and B use the same lane -> k map (both are read from LDS
 // by the same formula); the C/D layout is dtype-independent on gfx950 (col = lane & 15, row = 4 (lane >> 4) + reg).
@@ -57,7 +57,7 @@ void dd_gemm8_kernel(const Gemm8Params p) {
   const int wm = wave >> 1, wn = wave & 1;
   const int c = lane & 15, g = lane >> 4;
 
-  // XCD-aware tile order (csrc/gemm.hip): the tiles of one XCD share activation panels
+  // XCD-aware tile order (csrc/gemm_device.h): the tiles of one XCD share activation panels
   const int ntiles = p.tiles_m * p.tiles_n;
   const int xcd = blockIdx.x & 7, xq = ntiles >> 3, xr = ntiles & 7;
   const int tile = ((xcd < xr) ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (blockIdx.x >> 3);

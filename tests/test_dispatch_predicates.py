@@ -166,3 +166,69 @@ def test_layernorm_fold_plans_without_a_tuned_tile():
             g.alpha, g.ln_eps, g.epilogue = 1.0, 1e-5, 1
             name = lib.dd_gemm_kernel_name(ctypes.byref(g)).decode()
             assert name.startswith("dd_gemm2_kernel<") and name.split(">")[0].endswith("true"), (rows, k, name)
+
+
+def _mangled_prefix(kernel):
+    """`dd_gemm2_kernel<_Float16, 2, 2, 4, 4, 3, true, false>` -> the start of its symbol, up to the closing E of the
+    template arguments: _ZN12_GLOBAL__N_1 <len><name> I DF16_ Li2E ... Lb0E E (the kernels live in an anonymous namespace)."""
+    base, args = kernel.rstrip(">").split("<")
+    enc = {"_Float16": "DF16_", "__bf16": "DF16b", "true": "Lb1E", "false": "Lb0E"}
+    return ("_ZN12_GLOBAL__N_1%d%sI%sE" % (len(base), base, "".join(enc.get(a) or "Li%dE" % int(a) for a in args.split(", ")))).encode()
+
+
+def test_every_plan_names_a_kernel_the_library_holds():
+    """The planner, the launchers and dd_gemm_kernel_name read one tile table: for every tile id and every form the answer is
+    `unsupported`, `invalid`, or a kernel whose symbol is in the built library — never a kernel dd_gemm would then refuse
+    (conv + GEGLU was planned and named on 11 tiles, 12 kernels that were never instantiated, until validate rejected it)."""
+    from dualdiff_amd import _build
+    lib = _native.load()
+    blob = open(_build.lib_path(), "rb").read()
+    tiles = [lib.dd_gemm_tile_id(i) for i in range(lib.dd_gemm_num_tiles())] + [0]
+    assert len(tiles) == len(set(tiles)) and all(t >= 0 for t in tiles)
+
+    def dense(rows, n, k, epilogue=0, ln_out=False):
+        d = _native.GemmDesc()
+        d.a = d.w = d.out = 4096
+        d.rows, d.n, d.k, d.k1, d.lda, d.ldc, d.alpha, d.epilogue = rows, n, k, k, k, n, 1.0, epilogue
+        if ln_out:
+            d.ln_out = d.lno_gamma = d.lno_beta = 4096
+            d.ld_ln_out = n
+        return d
+
+    def conv(h, w, cin, cout, stride=1, pad_lo=1, epilogue=0):
+        ho, wo = (h + pad_lo + 1 - 3) // stride + 1, (w + pad_lo + 1 - 3) // stride + 1
+        d = _conv_desc(6, h, w, cin, cout, 0)
+        d.rows, d.hout, d.wout, d.stride, d.epilogue = 6 * ho * wo, ho, wo, stride, epilogue
+        return d
+
+    # rows below and beyond one residency generation of every tile, K in whole 64-element steps and not (the LDS-DMA
+    # families' precondition), images that fit the direct conv, its band form, and neither
+    forms = {"dense": [(dense(r, n, k), 1) for r in (12, 1092, 67200) for n, k in ((320, 320), (1280, 1288))],
+             "GEGLU": [(dense(r, n, k, 1), 1) for r in (12, 1092, 67200) for n, k in ((1280, 320), (1280, 1288))],
+             "SiLU": [(dense(r, n, k, 2), 1) for r in (12, 67200) for n, k in ((320, 320), (1280, 1288))],
+             "ln_out": [(dense(r, 320, k, 0, True), 1) for r in (1092, 67200) for k in (320, 1280)],
+             "conv": [(conv(h, w, cin, 320, s), 1) for h, w in ((28, 50), (14, 25), (112, 220)) for cin in (320, 8) for s in (1, 2)],
+             "conv + GEGLU": [(conv(h, w, cin, 320, 1, 1, 1), 1) for h, w in ((28, 50), (14, 25)) for cin in (320, 8)],
+             "pad-0 conv": [(conv(h, w, cin, 320, 2, 0), 0) for h, w in ((28, 50), (14, 25)) for cin in (320, 8)]}
+    named, missing = set(), set()
+    for form, cases in forms.items():
+        for (d, pad_lo), tile, dtype in [(c, t, dt) for c in cases for t in tiles for dt in (0, 1)]:
+            d.tile, d.dtype = tile, dtype
+            names = [lib.dd_gemm_conv_pad_kernel_name(ctypes.byref(d), pad_lo).decode()]
+            if pad_lo == 1:
+                names.append(lib.dd_gemm_kernel_name(ctypes.byref(d)).decode())
+                assert names[0] == names[1], (form, tile, names)
+            if names[0] in ("unsupported", "invalid"):
+                assert lib.dd_gemm_conv_pad_workspace_bytes(ctypes.byref(d), pad_lo) == 0, (form, tile)
+                continue
+            kernel = names[0].split(" split=")[0]
+            named.add(kernel)
+            if _mangled_prefix(kernel) not in blob:
+                missing.add((form, kernel))
+    assert not missing, sorted(missing)
+    # not vacuous: every family was planned, in both dtypes
+    for family in ("dd_gemm_kernel<", "dd_gemm_pad0_kernel<", "dd_gemm2_kernel<", "dd_gemm3_kernel<", "dd_gemm4_kernel<",
+                   "dd_conv3s_kernel<"):
+        for t in ("_Float16", "__bf16"):
+            assert any(k.startswith(family + t) for k in named), (family, t)
+    assert len(named) >= 100, len(named)

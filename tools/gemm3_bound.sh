@@ -1,20 +1,23 @@
 #!/bin/bash
 # GPU box: the pipelined dense family against its own sides: product, no LDS-DMA (-DDD_DBG_NODMA), no matrix instructions
-# (-DDD_DBG_NOMFMA), quick builds of the pipelined family only (-DDD_DBG_ONLY_P)
+# (-DDD_DBG_NOMFMA): builds of the family's translation unit (csrc/gemm23.hip) only
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p gpurun_out; export TMPDIR=/tmp
 R=$PWD; L=$R/dualdiff_amd/lib
 [ -f $L/obj/norm.o ] || python3 -c "from dualdiff_amd import _build; _build.build_native(force=True)" 2>/dev/null
 VARS="${G3_VARIANTS:-NODMA NOMFMA}"
+SRCS="gemm23"     # the translation units of the kernels under test; every other object is the product's
 for V in $VARS; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 -std=c++17 -fPIC -Wno-unused-value -DNDEBUG -mllvm -amdgpu-mfma-vgpr-form=1 \
-    -DDD_DBG_ONLY_P $(for f in $(echo $V | tr + ' '); do echo -n "-DDD_DBG_$f "; done) -c $R/dualdiff_amd/csrc/gemm.hip -o /tmp/gemm_$V.o &
+  for S in $SRCS; do
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 -std=c++17 -fPIC -Wno-unused-value -DNDEBUG -mllvm -amdgpu-mfma-vgpr-form=1 \
+      $(for f in $(echo $V | tr + ' '); do echo -n "-DDD_DBG_$f "; done) -c $R/dualdiff_amd/csrc/$S.hip -o /tmp/${S}_$V.o &
+  done
 done
 wait
-OBJS=$(ls $L/obj/*.o | grep -v "/gemm.o")
+OBJS=$(ls $L/obj/*.o | grep -v -E "/($(echo $SRCS | tr ' ' '|'))\.o")
 OUT=gpurun_out/${G3_OUT:-r05_gemm3_bound.txt}; rm -f $OUT
 python3 tools/gemm3_sides.py product 2>&1 | grep -v amdgpu.ids | tee -a $OUT
 for V in $VARS; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o /tmp/libdd_g3_$V.so /tmp/gemm_$V.o $OBJS
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o /tmp/libdd_g3_$V.so $(for S in $SRCS; do echo /tmp/${S}_$V.o; done) $OBJS
   DD_HIP_LIB=/tmp/libdd_g3_$V.so python3 tools/gemm3_sides.py $V 2>&1 | grep -v amdgpu.ids | tee -a $OUT
 done
