@@ -3,325 +3,54 @@
 Every function launches hand-written gfx950 kernels from libdualdiff_hip.so on torch's
 current stream.  Tensors are token-major / NHWC 2-D views (rows, channels) in fp16 or bf16.
 There is no eager fallback: a non-GPU tensor raises.
+
+The scratch buffers live in _workspace, the per-launch timing in _timer, the tile / split-K tuner and its table in
+tuning; their public names are re-exported here.
 """
 import collections as _collections
 import ctypes
-import threading as _threading
+import os as _os
 
 import torch
 
-from . import _native
+from . import _native, _timer, _workspace, tuning
 from ._native import DD_BF16, DD_EPI_GEGLU, DD_EPI_NONE, DD_EPI_SILU, DD_F16, AttnDesc, Gemm8Desc, GemmDesc, XAttnDesc
+from ._timer import KernelTimer, _stream, set_timer  # noqa: F401
+from ._workspace import workspace, workspace_owner  # noqa: F401
+from .tuning import (CHALLENGE_TILES, TUNE_TABLE_PATH, forget_tuned, load_tuned, save_tuned,  # noqa: F401
+                     tune_candidates, tuned_table)
 
-_WS = {}
-_WS_MIN_BYTES = 64 << 20
-
-
-class KernelTimer:
-    """Optional per-launch HIP-event timing of the MFMA kernels (bench.py roofline leg).
-
-    When installed (`ops.set_timer(KernelTimer())`) every gemm / conv3x3 / attention launch is
-    bracketed by events recorded on the stream the kernel is launched on; `summary()` groups the
-    launches by kernel symbol and returns count, total time and algorithmic FLOPs."""
-
-    def __init__(self, shapes=False):
-        self.records = []
-        self.shapes = shapes
-        self.overhead_ms = 0.0
-        self.empty_bracket_ms = 0.0
-        self.probe_ms = 0.0
-
-    def calibrate(self, n=48, probe_us=15.0):
-        """Event overhead per bracket, MEASURED at run time (not a fitted constant) and subtracted in
-        summary() so that the per-kernel averages are comparable with rocprofv3's kernel durations.
-
-        Probe: dd_probe_spin — one wave that busy-waits `probe_us` on the constant 100 MHz s_memrealtime counter and
-        stores its own first and last reading, i.e. a kernel whose DEVICE-SIDE duration is known without events or a
-        profiler.  n such launches are bracketed like the kernels of the instrumented step (queue kept busy);
-        overhead = median(bracket - in-kernel duration): what an event pair adds around a ~15 us kernel (the
-        dominant classes are 15-45 us).  A first attempt subtracted a probe's back-to-back time instead; that time
-        contains the launch-to-launch gap a profiler does not count and gave 0.  The empty-bracket figure
-        (4.6-4.8 us on MI355X) is kept in `empty_bracket_ms` for the JSON line; kernels of ~5 us stay the least
-        certain rows of the table."""
-        lib = _native.load()
-        st = torch.cuda.current_stream()
-        dev = torch.device("cuda", torch.cuda.current_device())
-        pairs = []
-        for _ in range(n):
-            e0 = torch.cuda.Event(enable_timing=True)
-            e1 = torch.cuda.Event(enable_timing=True)
-            e0.record(st)
-            e1.record(st)
-            pairs.append((e0, e1))
-        torch.cuda.synchronize()
-        d = sorted(a.elapsed_time(b) for a, b in pairs)
-        self.empty_bracket_ms = d[len(d) // 2]
-        stamps = torch.zeros((n, 2), dtype=torch.int64, device=dev)
-        ticks = int(probe_us * 100)
-        backlog = torch.empty(64 << 20, dtype=torch.uint8, device=dev)
-        for _ in range(40):                       # keep the GPU behind the host while the brackets are enqueued
-            backlog.zero_()
-        pairs = []
-        for i in range(n):
-            a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a0.record(st)
-            _native.check(lib.dd_probe_spin(ctypes.c_void_p(stamps[i].data_ptr()), ticks, _stream()), "probe_spin")
-            a1.record(st)
-            pairs.append((a0, a1))
-        torch.cuda.synchronize()
-        inside = (stamps[:, 1] - stamps[:, 0]).double().cpu() * 1e-5          # 100 MHz ticks -> ms
-        over = sorted(p.elapsed_time(q) - float(inside[i]) for i, (p, q) in enumerate(pairs))
-        self.probe_ms = float(inside.median())
-        self.overhead_ms = min(max(over[len(over) // 2], 0.0), self.empty_bracket_ms)
-        return self.overhead_ms
-
-    def start(self):
-        e = torch.cuda.Event(enable_timing=True)
-        e.record(torch.cuda.current_stream())
-        return e
-
-    def stop(self, e0, name, flops, nbytes, staged=0.0):
-        """staged: bytes the launch moves from L2 into LDS (tiled GEMM / conv families: every tile re-stages its operand
-        slabs) — the quantity that actually bounds those kernels, reported beside the contract's roofs."""
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record(torch.cuda.current_stream())
-        self.records.append((name, flops, nbytes, e0, e1, staged))
-
-    def summary(self):
-        torch.cuda.synchronize()
-        out = {}
-        for name, flops, nbytes, e0, e1, staged in self.records:
-            d = out.setdefault(name, {"count": 0, "ms": 0.0, "flops": 0.0, "bytes": 0.0, "staged": 0.0})
-            d["count"] += 1
-            d["ms"] += max(e0.elapsed_time(e1) - self.overhead_ms, 0.0)
-            d["flops"] += flops
-            d["bytes"] += nbytes
-            d["staged"] += staged
-        return out
+_THIN_CONV = _os.environ.get("DD_THIN_CONV", "1") != "0"       # A/B switch of dd_conv3x3_thin
+# split-K reduce folded into the GroupNorm that consumes the conv's output (dd_groupnorm_splitk): 50 launches fewer per
+# step, bit-identical — and 0.5 % SLOWER on the step (84.9 vs 85.4 steps/s over three alternating pairs: the norm then
+# reads `split` fp32 slabs with the few workgroups a 28-pixel image gives it, where the separate reduce spreads them over
+# the chip), so it is OFF by default; DD_GN_SPLITK=1 turns it on
+GN_SPLITK = _os.environ.get("DD_GN_SPLITK", "0") == "1"
+LN_OUT_TILE = int(_os.environ.get("DD_LN_OUT_TILE", "0"))
+# dd_xattn320 owns 80-row tiles, one workgroup per CU (135 KB of LDS), and every workgroup re-stages both 205 KB weight
+# matrices: it beats the three-launch form while its grid is ONE residency generation (12 instances x 1400 rows = 210
+# workgroups on 256 CUs: 40 vs 45 us for the SFA module) and loses beyond it (48 instances = 840 workgroups: 127 vs 114 us,
+# profiles/r03_sfa_roofline.txt, VERDICT r3 weak #3).  Above this many workgroups the callers take the three launches.
+XATTN_MAX_WGS = int(_os.environ.get("DD_XATTN_MAX_WGS", "256"))
+CAUSAL_ATTN_MAX_L = 128         # DD_CAUSAL_ATTN_MAX_L of include/dualdiff_hip.h
+_ZERO_BIAS = {}
+_FDT = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}
 
 
-_TIMER = None
-
-# ---- run-time tile / split-K selection ---------------------------------------------------------
-# The step touches a finite set of GEMM / conv shapes.  On first (eager, non-captured) use of a
-# shape every tile config x split-K candidate of dd_gemm is timed with HIP events on a scratch
-# output and the fastest is cached; graph capture then records the tuned launches.
-# DD_AUTOTUNE=0 falls back to the built-in heuristic of csrc/gemm.hip.
-import os as _os
-
-_AUTOTUNE = _os.environ.get("DD_AUTOTUNE", "1") != "0"
-_TUNED = {}
-_TILES = None           # filled from the library (dd_gemm_tile_id) on first use
-_SPLITS = (1, 2, 3, 4, 5, 6, 8, 12, 16)
-
-
-def _entry(v):
-    """(tile, split-K, split-K form): tables written before round 3 carry two values (form 0 = two launches)."""
-    return (int(v[0]), int(v[1]), int(v[2]) if len(v) > 2 else 0)
-
-
-def tuned_table():
-    return dict(_TUNED)
-
-
-def save_tuned(path, merge=True):
-    """Persist the tuned (tile, split-K) table so a later process skips the timing sweep.  merge: entries of
-    an existing file that this process did not touch (other dtype, other batch) are kept."""
-    import ast
-    import json
-    entries = {}
-    if merge and _os.path.exists(path):
-        with open(path) as f:
-            for k, v in json.load(f).get("entries", []):
-                entries[ast.literal_eval(k)] = _entry(v)
-    entries.update(_TUNED)
-    _os.makedirs(_os.path.dirname(_os.path.abspath(path)), exist_ok=True)
-    with open(path, "w") as f:
-        json.dump({"arch": "gfx950", "entries": [[repr(k), list(v)] for k, v in sorted(entries.items(), key=repr)]}, f, indent=0)
-
-
-def load_tuned(path):
-    """Load a table written by save_tuned(); entries for shapes already tuned here are kept."""
-    import ast
-    import json
-    with open(path) as f:
-        blob = json.load(f)
-    if blob.get("arch") != "gfx950":
-        raise RuntimeError("tune cache %s is not for gfx950" % path)
-    n = 0
-    for k, v in blob["entries"]:
-        key = ast.literal_eval(k)
-        if key not in _TUNED:
-            _TUNED[key] = _entry(v)
-            n += 1
-    return n
-
-
-_COLD = _os.environ.get("DD_AUTOTUNE_COLD", "1") != "0"
-# DD_TUNE_CHALLENGE=52[,..]: tiles added after the tracked table was written are timed against every entry's incumbent
-# the first time its shape is met (bench.py --challenge-tiles writes the table back)
-CHALLENGE_TILES = tuple(int(t) for t in _os.environ.get("DD_TUNE_CHALLENGE", "").split(",") if t.strip())
-_CHALLENGED = set()
-_FLUSH = {}
-
-# The tuned table of the shapes the denoising step touches is TRACKED (dualdiff_amd/tuned/gfx950.json,
-# written by `bench.py --retune`) and loaded on first use, so every process launches the same kernels
-# for the same shapes and the bench's roofline line can be recomputed from profiles/.  Only shapes that
-# are not in the table are timed at run time.  DD_TUNE_TABLE=0 ignores the tracked table, DD_TUNE_TABLE=<path>
-# loads another one.
-TUNE_TABLE_PATH = _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), "tuned", "gfx950.json")
-_TABLE_LOADED = False
-
-
-def _load_default_table():
-    global _TABLE_LOADED
-    if _TABLE_LOADED:
-        return
-    _TABLE_LOADED = True
-    path = _os.environ.get("DD_TUNE_TABLE", TUNE_TABLE_PATH)
-    if path != "0" and _os.path.exists(path):
-        load_tuned(path)
-
-
-def forget_tuned():
-    """Drop every tuned entry (bench.py --retune) and do not read the tracked table again."""
-    global _TABLE_LOADED
-    _TUNED.clear()
-    _TABLE_LOADED = True
-
-
-def _flush_and_warm(device, warm):
-    """Puts the caches in the state a launch sees inside the step: weights COLD (a step streams
-    ~3.3 GB of them, far more than L2 + the 256 MiB Infinity Cache hold), activations just produced
-    by the previous kernel and therefore WARM."""
-    buf = _FLUSH.get(device)
-    if buf is None:
-        buf = _FLUSH[device] = torch.empty(320 << 20, dtype=torch.uint8, device=device)
-    buf.zero_()
-    for t in warm:
-        if t is not None:
-            t.sum()
-
-
-def _autotune(lib, d, key, out_shape, dtype, device, warm=(), pad_lo=1):
-    """pad_lo: the conv's top / left padding; 0 times the dd_gemm_conv_pad launches conv3x3(pad=0) will make."""
-    _load_default_table()
-    hit = _TUNED.get(key)
-    challenge = ()
-    if hit is not None:
-        if not CHALLENGE_TILES or key in _CHALLENGED or torch.cuda.is_current_stream_capturing():
-            return hit
-        # a new tile asks for the shapes of the tracked table: time the incumbent against the challengers only
-        _CHALLENGED.add(key)
-        challenge = tuple((c, sp, 0) for c in CHALLENGE_TILES for sp in sorted({1, max(1, int(hit[1]))}))
-    elif not _AUTOTUNE or torch.cuda.is_current_stream_capturing():
-        return 0, 0, 0
-    saved = (d.out, d.ldc, d.accumulate, d.tile, d.split_k, d.ws, d.ws_bytes)
-    scratch = torch.empty(out_shape, dtype=dtype, device=device)
-    d.out, d.ldc, d.accumulate = scratch.data_ptr(), scratch.stride(0), 0
-    best, best_t = (0, 0, 0), float("inf")
-    stream = _stream()
-    if pad_lo == 1:
-        launch, ws_bytes = lib.dd_gemm, lib.dd_gemm_workspace_bytes
-    else:
-        def launch(dp, st):
-            return lib.dd_gemm_conv_pad(dp, pad_lo, st)
-
-        def ws_bytes(dp):
-            return lib.dd_gemm_conv_pad_workspace_bytes(dp, pad_lo)
-
-    def timed(tile, split, iters, ink=0):          # ink: third entry of a table row (split-K form), always 0 since round 5
-        d.tile, d.split_k = tile, split
-        need = ws_bytes(ctypes.byref(d))
-        if need > 0:
-            ws = workspace(need, device)
-            d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * 4
-        if launch(ctypes.byref(d), stream) != 0:
-            return None
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        if not _COLD:
-            e0.record()
-            for _ in range(iters):
-                launch(ctypes.byref(d), stream)
-            e1.record()
-            e1.synchronize()
-            return e0.elapsed_time(e1) / iters
-        samples = []
-        for _ in range(iters):
-            _flush_and_warm(device, warm)
-            e0.record()
-            launch(ctypes.byref(d), stream)
-            e1.record()
-            e1.synchronize()
-            samples.append(e0.elapsed_time(e1))
-        samples.sort()
-        return samples[len(samples) // 2]         # median: one slow launch (clock ramp, a neighbour's burst) must not decide
-
-    if challenge:
-        t_inc = timed(hit[0], hit[1], 21, hit[2])
-        best, best_t = tuple(hit), (t_inc if t_inc is not None else float("inf"))
-        for tile, split, ink in challenge:
-            if (tile, split, ink) == tuple(hit):
-                continue
-            t = timed(tile, split, 5, ink)
-            if t is None or t > 1.1 * best_t:
-                continue
-            t = timed(tile, split, 21, ink)
-            if t is not None and t < 0.97 * best_t:          # a challenger must win by 3 %: the medians carry ~2 % of noise
-                best, best_t = (tile, split, ink), t
-        (d.out, d.ldc, d.accumulate, d.tile, d.split_k, d.ws, d.ws_bytes) = saved
-        if best != tuple(hit):
-            print("[tune] %s: %s -> %s (%.1f -> %.1f us)" % (key, tuple(hit), best, t_inc * 1e3, best_t * 1e3), flush=True)
-        _TUNED[key] = best
-        return best
-    cands = []
-    excl = {int(t) for t in _os.environ.get("DD_TUNE_EXCLUDE", "").split(",") if t.strip()}   # A/B experiments
-    for tile, split in tune_candidates(lib, d):
-        if tile in excl:
-            continue
-        for ink in (0,):
-            t = timed(tile, split, 3, ink)            # >= 3 samples per candidate, cold or hot
-            if t is not None:
-                cands.append((t, tile, split, ink))
-    # the coarse pass is noisy: re-time the front-runners with more launches
-    cands.sort()
-    for t, tile, split, ink in cands[:8]:
-        t2 = timed(tile, split, 15 if _COLD else 12, ink)
-        if t2 is not None and t2 < best_t:
-            best, best_t = (tile, split, ink), t2
-    (d.out, d.ldc, d.accumulate, d.tile, d.split_k, d.ws, d.ws_bytes) = saved
-    if best[0] == 0:
-        # no candidate launched: the call is one no kernel can run.  Caching (0, 0, 0) would let save_tuned() write
-        # it into the tracked table; the call itself goes on to the library's own plan and raises from there.
-        return best
-    _TUNED[key] = best
-    return best
-
-
-def tune_candidates(lib, d):
-    """(tile id, split-K) pairs the run-time tuner times for the call described by `d` — every tile of the library,
-    split-K only where the K loop keeps >= 4 steps per slab and the slabs stay within 4096 128x128 blocks.  The planner
-    may still turn a pair down (dd_gemm_kernel_name: "unsupported") or launch it in a normalised form."""
-    global _TILES
-    if _TILES is None:
-        _TILES = tuple(lib.dd_gemm_tile_id(i) for i in range(lib.dd_gemm_num_tiles()))
-    kt = (d.k + 63) // 64
-    blocks128 = ((d.rows + 127) // 128) * ((d.n + 127) // 128)
-    return [(tile, split) for tile in _TILES for split in _SPLITS
-            if split == 1 or not (d.epilogue == DD_EPI_GEGLU or kt < 4 * split or blocks128 * split > 4096)]
-
-
-def set_timer(t):
-    global _TIMER
-    _TIMER = t
+def _dtype_code(dtype):
+    if dtype == torch.float16:
+        return DD_F16
+    if dtype == torch.bfloat16:
+        return DD_BF16
+    raise TypeError("dualdiff_amd ops take fp16 / bf16 tensors, got %s" % dtype)
 
 
 def _dt(t):
-    if t.dtype == torch.float16:
-        return DD_F16
-    if t.dtype == torch.bfloat16:
-        return DD_BF16
-    raise TypeError("dualdiff_amd ops take fp16 / bf16 tensors, got %s" % t.dtype)
+    return _dtype_code(t.dtype)
+
+
+def _tname(code):
+    return "f16" if code == DD_F16 else "bf16"
 
 
 def _need_gpu(*ts):
@@ -331,116 +60,8 @@ def _need_gpu(*ts):
                                "there is no CPU fallback" % t.device)
 
 
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-_WS_IN_GRAPH = set()      # keys whose current buffer a captured HIP graph holds a raw pointer to
-_WS_RETIRED = []          # such buffers after they were outgrown: kept alive for the graphs that use them
-
-
-# diagnostic builds (-DDD_DBG_STAMP, tools/build_dbg_libs.sh) write phase stamps into the tail of the workspace
-_DBG_STAMP_WS = _os.environ.get("DD_DBG_STAMP_WS", "0") == "1"
-
-
-_WS_OWNER = _threading.local()
-
-
-class workspace_owner:
-    """`with workspace_owner(token):` scratch buffers handed out inside are keyed by `token` instead of the current
-    stream's handle.  model_base.ForwardGraphs records each model's graphs under its own token: torch's stream handles
-    are pooled and re-used, so two models' capture streams can share a handle — harmless while forward graphs replay one
-    after the other, a race once two models' graphs replay concurrently (round 6: sibling overlap)."""
-
-    def __init__(self, token):
-        self.token = token
-
-    def __enter__(self):
-        self.prev = getattr(_WS_OWNER, "token", None)
-        _WS_OWNER.token = self.token
-
-    def __exit__(self, *exc):
-        _WS_OWNER.token = self.prev
-
-
-def workspace(nbytes, device, kind="gemm"):
-    """Grow-only fp32 scratch buffer per (device, stream — or workspace_owner token —, kind): kernels on concurrent
-    streams must not share scratch, and the split-K buffer (whose leading counter region dd_gemm keeps at zero)
-    is never lent to GroupNorm.  Zero-filled on allocation; allocate before graph capture.
-    A buffer that was handed out during a capture is never freed (torch's stream handles are pooled and
-    re-used, so a later, larger eager workload can outgrow a buffer that a live graph still writes to)."""
-    owner = getattr(_WS_OWNER, "token", None)
-    key = (device.type, device.index if device.index is not None else torch.cuda.current_device(),
-           torch.cuda.current_stream().cuda_stream if owner is None else ("owner", owner), kind)
-    ws = _WS.get(key)
-    need = max(int(nbytes), _WS_MIN_BYTES)
-    capturing = torch.cuda.is_current_stream_capturing()
-    if ws is None or ws.numel() * 4 < need:
-        if capturing:
-            raise RuntimeError("workspace would have to grow during graph capture; run one eager "
-                               "warm-up step first")
-        if ws is not None and key in _WS_IN_GRAPH:
-            _WS_RETIRED.append(ws)
-            _WS_IN_GRAPH.discard(key)
-        ws = torch.zeros((need + 3) // 4, dtype=torch.float32, device=device)
-        _WS[key] = ws
-    if capturing:
-        _WS_IN_GRAPH.add(key)
-    return ws
-
-
-def _kname(lib, d):
-    full = lib.dd_gemm_kernel_name(ctypes.byref(d)).decode()
-    name, rest = full.split(" split=")
-    return name, int(rest.split(" ")[0])
-
-
-def _staged_bytes(lib, d):
-    """L2 -> LDS bytes of one dd_gemm launch, from its plan (`grid=MxN tile=BMxBN...`): every tile stages a
-    (BM + BN) x 64-element slab pair per K-step; the direct small-image conv stages its (BM + 64)-row activation slab
-    once per 64-channel chunk and a BN x 64 weight slab per (chunk, tap)."""
-    import re
-    full = lib.dd_gemm_kernel_name(ctypes.byref(d)).decode()
-    m = re.search(r"grid=(\d+)x(\d+) tile=(.*)$", full)
-    if m is None:
-        return 0.0
-    tiles = int(m.group(1)) * int(m.group(2))
-    t = re.search(r"(\d+)x(\d+)", m.group(3))
-    if t is None:
-        return 0.0
-    bm, bn = int(t.group(1)), int(t.group(2))
-    if "conv3s" in m.group(3):
-        chunks = d.cin // 64
-        return float(tiles) * chunks * ((bm + (88 if "band" in m.group(3) else 64)) * 128.0 + 9 * bn * 128.0)
-    ksteps = (d.k + 63) // 64
-    return float(tiles) * ksteps * (bm + bn) * 128.0
-
-
-def _timed_gemm(lib, d, what, suffix, flops, nbytes, rows, n):
-    """dd_gemm under the KernelTimer: a split-K GEMM's two launches are bracketed SEPARATELY (dd_gemm_desc.phase)
-    and booked under their own kernel symbols, so that every class of the roofline table is one kernel symbol
-    whose average duration can be checked against rocprofv3's."""
-    name, split = _kname(lib, d)
-    staged = _staged_bytes(lib, d)
-    if split <= 1:
-        e0 = _TIMER.start()
-        _native.check(lib.dd_gemm(ctypes.byref(d), _stream()), what)
-        _TIMER.stop(e0, name + suffix, flops, nbytes, staged)
-        return
-    slab = 4.0 * split * rows * n
-    d.phase = 1
-    e0 = _TIMER.start()
-    _native.check(lib.dd_gemm(ctypes.byref(d), _stream()), what)
-    _TIMER.stop(e0, name + suffix, flops, nbytes + slab, staged)     # operands once + the fp32 slabs written
-    d.phase = 2
-    e0 = _TIMER.start()
-    _native.check(lib.dd_gemm(ctypes.byref(d), _stream()), what)
-    _TIMER.stop(e0, "dd_splitk_reduce_kernel", 0.0, slab + 2.0 * rows * n)
-    d.phase = 0
 
 
 def _forget_derived(t):
@@ -451,11 +72,49 @@ def _forget_derived(t):
             delattr(t, a)
 
 
+def _out_or_new(out, shape, dtype, device, what):
+    """The tensor a wrapper writes: a fresh one (`shape` may be a tensor whose layout it takes: torch.empty_like), or
+    the caller's `out` — of the dtype the kernel stores, and without the attributes that described its old contents."""
+    if out is None:
+        return torch.empty_like(shape) if isinstance(shape, torch.Tensor) else torch.empty(shape, dtype=dtype, device=device)
+    if out.dtype != dtype:
+        raise TypeError("%s: out must be %s" % (what, dtype))
+    _forget_derived(out)
+    return out
+
+
 def _rows2d(t):
     if t.dim() != 2 or t.stride(1) != 1:
         raise ValueError("expected a 2-D tensor with unit inner stride, got shape %s stride %s"
                          % (tuple(t.shape), t.stride()))
     return t
+
+
+def _check_lk_dev(lk_dev):
+    if lk_dev is not None and (lk_dev.dtype != torch.int32 or lk_dev.numel() < 1):
+        raise TypeError("lk_dev must be an int32 device tensor")
+
+
+def _epilogue_side(d, dtype, bias, rowvec, rows_per_inst, res, out, alpha, accumulate, epilogue, tile, split_k):
+    """The output side of a GemmDesc, the same for gemm and conv3x3: alpha * (acc + bias + rowvec[row // rows_per_inst])
+    + res -> out, and the tile / split-K the caller asked for (0 = tuned)."""
+    d.bias = bias.data_ptr() if bias is not None else None
+    if rowvec is not None:
+        rowvec = _rows2d(rowvec)
+        d.rowvec = rowvec.data_ptr(); d.ld_rowvec = rowvec.stride(0); d.rows_per_inst = rows_per_inst
+    if res is not None:
+        res = _rows2d(res)
+        d.res = res.data_ptr(); d.ldres = res.stride(0)
+    out = _rows2d(out)
+    d.out = out.data_ptr(); d.ldc = out.stride(0)
+    d.alpha = alpha; d.accumulate = int(accumulate); d.epilogue = epilogue
+    d.dtype = dtype; d.tile = tile; d.split_k = split_k
+
+
+def _tune(L, d, key, out_shape, dtype, device, warm):
+    """Sets d.tile / d.split_k from the table or the run-time tuner.  CHALLENGE_TILES is read here, from this module, at
+    call time: bench.py --challenge-tiles assigns it after import."""
+    d.tile, d.split_k = tuning.tune(L, d, key, out_shape, dtype, device, warm, CHALLENGE_TILES)[:2]
 
 
 def gemm(a, w, bias=None, *, a2=None, res=None, rowvec=None, rows_per_inst=1, alpha=1.0,
@@ -493,12 +152,7 @@ def gemm(a, w, bias=None, *, a2=None, res=None, rowvec=None, rows_per_inst=1, al
             raise ValueError("head_major needs a plain epilogue, its own output and n % D == 0")
         hm_out = torch.empty((n // hd, rows, hd), dtype=a.dtype, device=a.device)
         out = hm_out.view(rows, n)           # same bytes; the kernel ignores ldc in this mode
-    if out is None:
-        out = torch.empty((rows, n), dtype=odt, device=a.device)
-    elif out.dtype != odt:
-        raise TypeError("gemm: out must be %s" % odt)
-    else:
-        _forget_derived(out)
+    out = _out_or_new(out, (rows, n), odt, a.device, "gemm")
     d = GemmDesc()
     d.out_f32 = int(bool(out_f32))
     if hm_out is not None:
@@ -509,18 +163,8 @@ def gemm(a, w, bias=None, *, a2=None, res=None, rowvec=None, rows_per_inst=1, al
         d.a2 = a2.data_ptr(); d.lda2 = a2.stride(0)
     d.rows, d.n, d.k = rows, n, k
     d.w = w.data_ptr()
-    d.bias = bias.data_ptr() if bias is not None else None
-    if rowvec is not None:
-        rowvec = _rows2d(rowvec)
-        d.rowvec = rowvec.data_ptr(); d.ld_rowvec = rowvec.stride(0); d.rows_per_inst = rows_per_inst
-    if res is not None:
-        res = _rows2d(res)
-        d.res = res.data_ptr(); d.ldres = res.stride(0)
-    out = _rows2d(out)
-    d.out = out.data_ptr(); d.ldc = out.stride(0)
-    d.alpha = alpha; d.accumulate = int(accumulate); d.epilogue = epilogue
     d.conv = 0
-    d.dtype = _dt(a); d.tile = tile; d.split_k = split_k
+    _epilogue_side(d, _dt(a), bias, rowvec, rows_per_inst, res, out, alpha, accumulate, epilogue, tile, split_k)
     if ln is not None:
         if bias is not None or a2 is not None:
             raise ValueError("gemm(ln=...) folds the bias and takes a single source")
@@ -556,39 +200,20 @@ def gemm(a, w, bias=None, *, a2=None, res=None, rowvec=None, rows_per_inst=1, al
             raise ValueError("ln_stats needs a plain epilogue and n % 32 == 0")
         stats_out = torch.empty((rows, n // 32, 2), dtype=torch.float32, device=a.device)
         d.ln_stats_out = stats_out.data_ptr()
+    L = tuning.launcher(lib)
     if tile == 0 and split_k == 0:
-        d.tile, d.split_k, _ = _autotune(lib, d, ("g", rows, n, k, epilogue, d.dtype, a2 is not None, ln is not None)
-                                      + (("f32",) if out_f32 else ()) + (("so",) if ln_stats else ())
-                                      + (("si",) if stats_in is not None else ())
-                                      + (("hm", head_major[0]) if head_major is not None else ())
-                                      + (("res",) if res is not None else ()) + (("acc",) if accumulate else ()),
-                                      (rows, n), odt, a.device, warm=(a, a2, res))
-    need = lib.dd_gemm_workspace_bytes(ctypes.byref(d))
-    if need > 0 or _DBG_STAMP_WS:
-        ws = workspace(need, a.device)
-        d.ws = ws.data_ptr(); d.ws_bytes = ws.numel() * 4
-    if _TIMER is not None:
-        _timed_gemm(lib, d, "gemm", " gemm %dx%dx%d" % (rows, n_w, k) if _TIMER.shapes else "", 2.0 * rows * n_w * k,
-                    2.0 * (rows * k + n_w * k + rows * n * (1 + (1 if d.res else 0) + (1 if d.accumulate else 0))),
-                    rows, n)
-    else:
-        _native.check(lib.dd_gemm(ctypes.byref(d), _stream()), "gemm")
+        key = tuning.gemm_key(rows, n, k, epilogue, d.dtype, a2 is not None, ln is not None, out_f32=out_f32,
+                              stats_out=ln_stats, stats_in=stats_in is not None,
+                              head_major=head_major[0] if head_major is not None else None, res=res is not None,
+                              acc=accumulate)
+        _tune(L, d, key, (rows, n), odt, a.device, (a, a2, res))
+    _workspace.attach(d, a.device, lambda: L.ws_bytes(d))
+    _timer.gemm_launch(L, d, "gemm", "gemm", n_w, rows * k)
     if stats_out is not None:
         out._ln_stats = stats_out
     if ln_second is not None:
         out._ln_out = ln_second
     return hm_out if hm_out is not None else out
-
-
-_THIN_CONV = _os.environ.get("DD_THIN_CONV", "1") != "0"       # A/B switch of dd_conv3x3_thin
-# split-K reduce folded into the GroupNorm that consumes the conv's output (dd_groupnorm_splitk): 50 launches fewer per
-# step, bit-identical — and 0.5 % SLOWER on the step (84.9 vs 85.4 steps/s over three alternating pairs: the norm then
-# reads `split` fp32 slabs with the few workgroups a 28-pixel image gives it, where the separate reduce spreads them over
-# the chip), so it is OFF by default; DD_GN_SPLITK=1 turns it on
-GN_SPLITK = _os.environ.get("DD_GN_SPLITK", "0") == "1"
-
-
-LN_OUT_TILE = int(_os.environ.get("DD_LN_OUT_TILE", "0"))
 
 
 def thin_conv_ok(cin, cout, stride, m):
@@ -628,101 +253,51 @@ def conv3x3(x, w, bias, m, hin, win, *, stride=1, up_size=None, rowvec=None, res
     if w.shape[1] != 9 * cin or not w.is_contiguous():
         raise ValueError("conv weight must be contiguous [cout, 9*cin]")
     rows = m * hout * wout
-    if out is None:
-        out = torch.empty((rows, cout), dtype=x.dtype, device=x.device)
-    else:
-        _forget_derived(out)
+    out = _out_or_new(out, (rows, cout), x.dtype, x.device, "conv3x3")
     if pad == 1 and thin_conv_ok(cin, cout, stride, m) and up_size is None and rowvec is None and res is None and alpha == 1.0 \
             and not accumulate and epilogue in (DD_EPI_NONE, DD_EPI_SILU) and tile == 0 and split_k == 0 \
             and out.is_contiguous():
         # thin channel counts on a large image (the condition embedder's first layers): patch-in-LDS direct conv
-        e0 = _TIMER.start() if _TIMER is not None else None
-        rc = lib.dd_conv3x3_thin(_ptr(x), _ptr(w), _ptr(bias), _ptr(out), m, hin, win, cin, cout, stride,
-                                 int(epilogue == DD_EPI_SILU), _dt(x), _stream())
-        _native.check(rc, "conv3x3_thin")
-        if _TIMER is not None:
-            _TIMER.stop(e0, "dd_conv3x3_thin_kernel" + (" conv %dx%dx%d" % (rows, cout, 9 * cin) if _TIMER.shapes else ""),
-                        2.0 * rows * cout * 9 * cin, 2.0 * (x.numel() + w.numel() + rows * cout))
+        def book():
+            suffix, flops, nbytes = _timer.mm_cost("conv", rows, cout, 9 * cin, x.numel(), cout)
+            return "dd_conv3x3_thin_kernel" + suffix, flops, nbytes
+        _timer.launch("conv3x3_thin", lib.dd_conv3x3_thin, _ptr(x), _ptr(w), _ptr(bias), _ptr(out), m, hin, win, cin, cout,
+                      stride, int(epilogue == DD_EPI_SILU), _dt(x), _stream(), book=book)
         return out
     d = GemmDesc()
     d.a = x.data_ptr(); d.lda = cin; d.k1 = 9 * cin
     d.rows, d.n, d.k = rows, cout, 9 * cin
     d.w = w.data_ptr()
-    d.bias = bias.data_ptr() if bias is not None else None
-    if rowvec is not None:
-        rowvec = _rows2d(rowvec)
-        d.rowvec = rowvec.data_ptr(); d.ld_rowvec = rowvec.stride(0); d.rows_per_inst = hout * wout
-    if res is not None:
-        res = _rows2d(res)
-        d.res = res.data_ptr(); d.ldres = res.stride(0)
-    out = _rows2d(out)
-    d.out = out.data_ptr(); d.ldc = out.stride(0)
-    d.alpha = alpha; d.accumulate = int(accumulate); d.epilogue = epilogue
     d.conv = 1
     d.hin, d.win, d.cin, d.hv, d.wv = hin, win, cin, hv, wv
     d.hout, d.wout, d.stride = hout, wout, stride
-    d.dtype = _dt(x); d.tile = tile; d.split_k = split_k
-    if pad == 0:
-        return _conv3x3_pad0(lib, d, x, res, out, m, rows, cout, cin, w)
+    _epilogue_side(d, _dt(x), bias, rowvec, hout * wout, res, out, alpha, accumulate, epilogue, tile, split_k)
+    L = tuning.launcher(lib, pad)
+    what = "conv3x3" if pad == 1 else "conv3x3(pad=0)"
     if tile == 0 and split_k == 0:
-        d.tile, d.split_k, _ = _autotune(lib, d, ("c", m, hin, win, cin, cout, stride, hv, wv, d.dtype),
-                                      (rows, cout), x.dtype, x.device, warm=(x, res))
-    need = lib.dd_gemm_workspace_bytes(ctypes.byref(d))
-    if need > 0 or _DBG_STAMP_WS:
-        ws = workspace(need, x.device)
-        d.ws = ws.data_ptr(); d.ws_bytes = ws.numel() * 4
-    if gn_next is not None and GN_SPLITK and need > 0 and alpha == 1.0 and not accumulate and epilogue == DD_EPI_NONE:
+        key = (tuning.conv_key if pad == 1 else tuning.conv_pad0_key)(m, hin, win, cin, cout, stride, hv, wv, d.dtype)
+        _tune(L, d, key, (rows, cout), x.dtype, x.device, (x, res))
+    need = _workspace.attach(d, x.device, lambda: L.ws_bytes(d))
+    if pad == 1 and gn_next is not None and GN_SPLITK and need > 0 and alpha == 1.0 and not accumulate \
+            and epilogue == DD_EPI_NONE:
         gmod, gsilu, want_x = gn_next
-        _, split = _kname(lib, d)
+        split = _timer.plan_of(L, d)[1]
         if split > 1 and lib.dd_groupnorm_is_fused(hout * wout, cout, gmod.num_groups):
             # partial slabs only; dd_groupnorm_splitk is reduce + epilogue + GroupNorm(+SiLU) in one launch
             y = torch.empty((rows, cout), dtype=x.dtype, device=x.device)
-            d.phase = 1
-            e0 = _TIMER.start() if _TIMER is not None else None
-            _native.check(lib.dd_gemm(ctypes.byref(d), _stream()), "conv3x3")
-            if e0 is not None:
-                name = _kname(lib, d)[0]
-                _TIMER.stop(e0, name + (" conv %dx%dx%d" % (rows, cout, 9 * cin) if _TIMER.shapes else ""),
-                            2.0 * rows * cout * 9 * cin, 2.0 * (x.numel() + w.numel()) + 4.0 * split * rows * cout,
-                            _staged_bytes(lib, d))
-                e0 = _TIMER.start()
-            rc = lib.dd_groupnorm_splitk(ctypes.c_void_p(ws.data_ptr() + 65536), split, _ptr(bias), _ptr(rowvec),
-                                         rowvec.stride(0) if rowvec is not None else 0, _ptr(res),
-                                         res.stride(0) if res is not None else 0, _ptr(out) if want_x else None,
-                                         _ptr(gmod.weight), _ptr(gmod.bias), _ptr(y), m, hout * wout, cout,
-                                         gmod.num_groups, float(gmod.eps), int(gsilu), _dt(x), _stream())
-            _native.check(rc, "groupnorm_splitk")
-            if e0 is not None:
-                _TIMER.stop(e0, "dd_gn_splitk_kernel", 0.0, 4.0 * split * rows * cout + 2.0 * rows * cout * (2 if want_x else 1))
+            _timer.gemm_launch(L, d, what, "conv", cout, x.numel(), reduce=False)
+            _timer.launch("groupnorm_splitk", lib.dd_groupnorm_splitk, ctypes.c_void_p(d.ws + 65536), split, _ptr(bias),
+                          _ptr(rowvec), rowvec.stride(0) if rowvec is not None else 0, _ptr(res),
+                          res.stride(0) if res is not None else 0, _ptr(out) if want_x else None,
+                          _ptr(gmod.weight), _ptr(gmod.bias), _ptr(y), m, hout * wout, cout,
+                          gmod.num_groups, float(gmod.eps), int(gsilu), _dt(x), _stream(),
+                          book=lambda: ("dd_gn_splitk_kernel", 0.0,
+                                        4.0 * split * rows * cout + 2.0 * rows * cout * (2 if want_x else 1)))
             out._gn_cache = (gmod, bool(gsilu), y)
             if not want_x:
                 out._unwritten = True          # nobody but that GroupNorm may read it
             return out
-    if _TIMER is not None:
-        _timed_gemm(lib, d, "conv3x3", " conv %dx%dx%d" % (rows, cout, 9 * cin) if _TIMER.shapes else "",
-                    2.0 * rows * cout * 9 * cin,
-                    2.0 * (x.numel() + w.numel() + rows * cout * (1 + (1 if d.res else 0) + (1 if d.accumulate else 0))),
-                    rows, cout)
-        return out
-    _native.check(lib.dd_gemm(ctypes.byref(d), _stream()), "conv3x3")
-    return out
-
-
-def _conv3x3_pad0(lib, d, x, res, out, m, rows, cout, cin, w):
-    """conv3x3(pad=0): tuned under its own key (the pad-1 keys are untouched), launched through dd_gemm_conv_pad."""
-    if d.tile == 0 and d.split_k == 0:
-        d.tile, d.split_k, _ = _autotune(lib, d, ("c", m, d.hin, d.win, cin, cout, d.stride, d.hv, d.wv, d.dtype, "p0"),
-                                      (rows, cout), x.dtype, x.device, warm=(x, res), pad_lo=0)
-    need = lib.dd_gemm_conv_pad_workspace_bytes(ctypes.byref(d), 0)
-    if need > 0 or _DBG_STAMP_WS:
-        ws = workspace(need, x.device)
-        d.ws = ws.data_ptr(); d.ws_bytes = ws.numel() * 4
-    e0 = _TIMER.start() if _TIMER is not None else None
-    _native.check(lib.dd_gemm_conv_pad(ctypes.byref(d), 0, _stream()), "conv3x3(pad=0)")
-    if e0 is not None:
-        name = lib.dd_gemm_conv_pad_kernel_name(ctypes.byref(d), 0).decode().split(" split=")[0]
-        _TIMER.stop(e0, name + (" conv %dx%dx%d" % (rows, cout, 9 * cin) if _TIMER.shapes else ""), 2.0 * rows * cout * 9 * cin,
-                    2.0 * (x.numel() + w.numel() + rows * cout * (1 + (1 if d.res else 0) + (1 if d.accumulate else 0))))
+    _timer.gemm_launch(L, d, what, "conv", cout, x.numel())
     return out
 
 
@@ -753,20 +328,16 @@ def groupnorm(x, gamma, beta, m, hw, groups, eps, silu, x2=None, out=None):
     c2 = x2.shape[1] if x2 is not None else 0
     if not x.is_contiguous() or (x2 is not None and not x2.is_contiguous()):
         raise ValueError("groupnorm inputs must be contiguous")
-    if out is None:
-        out = torch.empty((m * hw, c1 + c2), dtype=x.dtype, device=x.device)
+    out = _out_or_new(out, (m * hw, c1 + c2), x.dtype, x.device, "groupnorm")
     need = lib.dd_groupnorm_workspace_bytes(m, groups)
     ws = workspace(need, x.device, "gn")
-    e0 = _TIMER.start() if _TIMER is not None else None
-    rc = lib.dd_groupnorm_nhwc(_ptr(x), c1, _ptr(x2), c2, _ptr(gamma), _ptr(beta), _ptr(out),
-                               m, hw, groups, eps, int(silu), _dt(x), _ptr(ws), ws.numel() * 4,
-                               _stream())
-    _native.check(rc, "groupnorm")
-    if e0 is not None:      # HBM-bound: each element read once and written once
+
+    def book():      # HBM-bound: each element read once and written once
         th = lib.dd_groupnorm_is_fused(hw, c1 + c2, groups)
-        _TIMER.stop(e0, "dd_gn_fused_kernel<%s, %d, 8>" % ("f16" if x.dtype == torch.float16 else "bf16", th) if th
-                    else "dd_gn_stats_kernel + dd_gn_apply_kernel (2 launches)",
-                    0.0, (4.0 if th else 6.0) * out.numel())
+        return ("dd_gn_fused_kernel<%s, %d, 8>" % (_tname(_dt(x)), th) if th
+                else "dd_gn_stats_kernel + dd_gn_apply_kernel (2 launches)", 0.0, (4.0 if th else 6.0) * out.numel())
+    _timer.launch("groupnorm", lib.dd_groupnorm_nhwc, _ptr(x), c1, _ptr(x2), c2, _ptr(gamma), _ptr(beta), _ptr(out),
+                  m, hw, groups, eps, int(silu), _dt(x), _ptr(ws), ws.numel() * 4, _stream(), book=book)
     return out
 
 
@@ -776,14 +347,9 @@ def layernorm(x, gamma, beta, eps=1e-5, out=None):
     x = _rows2d(x)
     if not x.is_contiguous():
         raise ValueError("layernorm input must be contiguous")
-    if out is None:
-        out = torch.empty_like(x)
-    e0 = _TIMER.start() if _TIMER is not None else None
-    rc = lib.dd_layernorm(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(out), x.shape[0], x.shape[1],
-                          eps, _dt(x), _stream())
-    _native.check(rc, "layernorm")
-    if e0 is not None:
-        _TIMER.stop(e0, "dd_layernorm", 0.0, 4.0 * out.numel())
+    out = _out_or_new(out, x, x.dtype, x.device, "layernorm")
+    _timer.launch("layernorm", lib.dd_layernorm, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(out), x.shape[0], x.shape[1],
+                  eps, _dt(x), _stream(), book=lambda: ("dd_layernorm", 0.0, 4.0 * out.numel()))
     return out
 
 
@@ -811,8 +377,7 @@ def attention(q, k, v, batch, lq, lk, heads, head_dim, scale=None, *, kv_batch_m
     serves every context length up to the capacity)."""
     lib = _native.load()
     _need_gpu(q, k, v, out, kv_batch_map, kv_batch_map2, lk_dev)
-    if lk_dev is not None and (lk_dev.dtype != torch.int32 or lk_dev.numel() < 1):
-        raise TypeError("lk_dev must be an int32 device tensor")
+    _check_lk_dev(lk_dev)
     if kv_batch_map2 is not None and (kv_batch_map is None or seq_strides is not None):
         raise ValueError("kv_batch_map2 needs kv_batch_map and no seq_strides")
     if kv_seq_strides is not None and seq_strides is None:
@@ -838,10 +403,8 @@ def attention(q, k, v, batch, lq, lk, heads, head_dim, scale=None, *, kv_batch_m
     d.k, d.ldk, d.k_batch_stride, d.k_head_stride = operand(k, lk)
     d.v, d.ldv, d.v_batch_stride, d.v_head_stride = operand(v, lk)
     d.q_prescaled = int(bool(q_prescaled))
-    if out is None:
-        out = torch.empty((q.shape[0], heads * head_dim) if seq_strides is not None else
-                          (batch * lq, heads * head_dim), dtype=q.dtype, device=q.device)
-    out = _rows2d(out)
+    out = _rows2d(_out_or_new(out, (q.shape[0] if seq_strides is not None else batch * lq, heads * head_dim), q.dtype,
+                              q.device, "attention"))
     d.o, d.ldo = out.data_ptr(), out.stride(0)
     d.o_batch_stride = lq * out.stride(0)
     if seq_strides is not None:
@@ -873,18 +436,11 @@ def attention(q, k, v, batch, lq, lk, heads, head_dim, scale=None, *, kv_batch_m
             d.o = base[3] + b0 * d.o_batch_stride * es
             _native.check(lib.dd_attention(ctypes.byref(d), _stream()), "attention")
         return out
-    if _TIMER is not None:
-        e0 = _TIMER.start()
-        _native.check(lib.dd_attention(ctypes.byref(d), _stream()), "attention")
-        _TIMER.stop(e0, "dd_attn5_kernel<%s,D%d>" % ("f16" if d.dtype == DD_F16 else "bf16", head_dim),
-                    4.0 * batch * heads * lq * lk * head_dim * npair,
-                    2.0 * heads * head_dim * batch * (2 * lq + 2 * lk * npair))
-        return out
-    _native.check(lib.dd_attention(ctypes.byref(d), _stream()), "attention")
+    _timer.launch("attention", lib.dd_attention, ctypes.byref(d), _stream(),
+                  book=lambda: ("dd_attn5_kernel<%s,D%d>" % (_tname(d.dtype), head_dim),
+                                4.0 * batch * heads * lq * lk * head_dim * npair,
+                                2.0 * heads * head_dim * batch * (2 * lq + 2 * lk * npair)))
     return out
-
-
-CAUSAL_ATTN_MAX_L = 128         # DD_CAUSAL_ATTN_MAX_L of include/dualdiff_hip.h
 
 
 def causal_attention(q, k, v, batch, l, heads, head_dim, out=None):
@@ -898,21 +454,14 @@ def causal_attention(q, k, v, batch, l, heads, head_dim, out=None):
         if t.shape[0] != batch * l or t.shape[1] < heads * head_dim or t.dtype != q.dtype:
             raise ValueError("causal_attention operands must be (%d, >= %d) %s views, got %s %s"
                              % (batch * l, heads * head_dim, q.dtype, tuple(t.shape), t.dtype))
-    if out is None:
-        out = torch.empty((batch * l, heads * head_dim), dtype=q.dtype, device=q.device)
-    elif out.shape[0] != batch * l or out.shape[1] < heads * head_dim or out.dtype != q.dtype:
+    if out is not None and (out.shape[0] != batch * l or out.shape[1] < heads * head_dim or out.dtype != q.dtype):
         raise ValueError("causal_attention: out must be (%d, >= %d) %s" % (batch * l, heads * head_dim, q.dtype))
-    else:
-        _forget_derived(out)
-    out = _rows2d(out)
-    e0 = _TIMER.start() if _TIMER is not None else None
-    rc = lib.dd_causal_attention(_ptr(q), _ptr(k), _ptr(v), _ptr(out), q.stride(0), k.stride(0), v.stride(0),
-                                 out.stride(0), l * q.stride(0), l * k.stride(0), l * v.stride(0), l * out.stride(0),
-                                 batch, l, heads, head_dim, float(head_dim) ** -0.5, _dt(q), _stream())
-    _native.check(rc, "causal_attention")
-    if e0 is not None:
-        _TIMER.stop(e0, "dd_causal_attn_kernel<%s>" % ("f16" if q.dtype == torch.float16 else "bf16"),
-                    2.0 * batch * heads * l * l * head_dim, 2.0 * heads * head_dim * batch * l * 4)
+    out = _rows2d(_out_or_new(out, (batch * l, heads * head_dim), q.dtype, q.device, "causal_attention"))
+    _timer.launch("causal_attention", lib.dd_causal_attention, _ptr(q), _ptr(k), _ptr(v), _ptr(out), q.stride(0),
+                  k.stride(0), v.stride(0), out.stride(0), l * q.stride(0), l * k.stride(0), l * v.stride(0),
+                  l * out.stride(0), batch, l, heads, head_dim, float(head_dim) ** -0.5, _dt(q), _stream(),
+                  book=lambda: ("dd_causal_attn_kernel<%s>" % _tname(_dt(q)), 2.0 * batch * heads * l * l * head_dim,
+                                2.0 * heads * head_dim * batch * l * 4))
     return out
 
 
@@ -935,16 +484,6 @@ def clip_embed(ids, tok, pos, eos_token_id):
                            int(eos_token_id), _dt(tok), _stream())
     _native.check(rc, "clip_embed")
     return rows, pool
-
-
-_ZERO_BIAS = {}
-
-
-# dd_xattn320 owns 80-row tiles, one workgroup per CU (135 KB of LDS), and every workgroup re-stages both 205 KB weight
-# matrices: it beats the three-launch form while its grid is ONE residency generation (12 instances x 1400 rows = 210
-# workgroups on 256 CUs: 40 vs 45 us for the SFA module) and loses beyond it (48 instances = 840 workgroups: 127 vs 114 us,
-# profiles/r03_sfa_roofline.txt).  Above this many workgroups the callers take the three launches.
-XATTN_MAX_WGS = int(_os.environ.get("DD_XATTN_MAX_WGS", "256"))
 
 
 def xattn320_ok(c, heads, lk, rows=None):
@@ -986,8 +525,7 @@ def xattn320(x, wq, wo, bo, k, v, instances, rows_per_inst, lk, scale, *, res=No
     the capacity of the K / V layout."""
     lib = _native.load()
     _need_gpu(x, wq, wo, bo, k, v, res, out, lk_dev)
-    if lk_dev is not None and (lk_dev.dtype != torch.int32 or lk_dev.numel() < 1):
-        raise TypeError("lk_dev must be an int32 device tensor")
+    _check_lk_dev(lk_dev)
     x = _rows2d(x)
     rows = instances * rows_per_inst
     if x.shape != (rows, 320):
@@ -1002,11 +540,7 @@ def xattn320(x, wq, wo, bo, k, v, instances, rows_per_inst, lk, scale, *, res=No
         if t.shape[0] != instances * lk or t.shape[1] < 320:
             raise ValueError("row-major K / V must be (instances * lk, >= 320)")
         return t.data_ptr(), t.stride(0), lk * t.stride(0), 40
-    if out is None:
-        out = torch.empty((rows, 320), dtype=x.dtype, device=x.device)
-    else:
-        _forget_derived(out)
-    out = _rows2d(out)
+    out = _rows2d(_out_or_new(out, (rows, 320), x.dtype, x.device, "xattn320"))
     wqp, wop = _xpacked(wq), _xpacked(wo)
     d = XAttnDesc()
     d.x, d.ldx = x.data_ptr(), x.stride(0)
@@ -1033,12 +567,11 @@ def xattn320(x, wq, wo, bo, k, v, instances, rows_per_inst, lk, scale, *, res=No
         second = torch.empty((rows, 320), dtype=x.dtype, device=x.device)
         d.ln_out, d.ld_ln_out = second.data_ptr(), 320
         d.ln_gamma, d.ln_beta, d.ln_eps = g_.data_ptr(), b_.data_ptr(), float(eps_)
-    e0 = _TIMER.start() if _TIMER is not None else None
-    _native.check(lib.dd_xattn320(ctypes.byref(d), _stream()), "xattn320")
-    if e0 is not None:      # 2 projections + attention; bytes: x in, out out (+ res, + ln_out), weights, K / V
-        _TIMER.stop(e0, "dd_xattn320_kernel", 4.0 * rows * 320 * 320 + 4.0 * rows * lk * 320,
-                    2.0 * (rows * 320 * (2 + (1 if res is not None else 0) + (1 if second is not None else 0))
-                           + 2 * 320 * 320 + 2 * instances * lk * 320))
+    # 2 projections + attention; bytes: x in, out out (+ res, + ln_out), weights, K / V
+    _timer.launch("xattn320", lib.dd_xattn320, ctypes.byref(d), _stream(),
+                  book=lambda: ("dd_xattn320_kernel", 4.0 * rows * 320 * 320 + 4.0 * rows * lk * 320,
+                                2.0 * (rows * 320 * (2 + (1 if res is not None else 0) + (1 if second is not None else 0))
+                                       + 2 * 320 * 320 + 2 * instances * lk * 320)))
     if second is not None:
         out._ln_out = second
     return out
@@ -1047,23 +580,16 @@ def xattn320(x, wq, wo, bo, k, v, instances, rows_per_inst, lk, scale, *, res=No
 def add(a, b, c=None, out=None):
     lib = _native.load()
     _need_gpu(a, b, c, out)
-    if out is None:
-        out = torch.empty_like(a)
-    else:
-        _forget_derived(out)
-    e0 = _TIMER.start() if _TIMER is not None else None
-    rc = lib.dd_add(_ptr(a), _ptr(b), _ptr(c), _ptr(out), a.numel(), _dt(a), _stream())
-    _native.check(rc, "add")
-    if e0 is not None:
-        _TIMER.stop(e0, "dd_add", 0.0, 2.0 * a.numel() * (3 + (1 if c is not None else 0)))
+    out = _out_or_new(out, a, a.dtype, a.device, "add")
+    _timer.launch("add", lib.dd_add, _ptr(a), _ptr(b), _ptr(c), _ptr(out), a.numel(), _dt(a), _stream(),
+                  book=lambda: ("dd_add", 0.0, 2.0 * a.numel() * (3 + (1 if c is not None else 0))))
     return out
 
 
 def scale(x, s, out=None):
     lib = _native.load()
     _need_gpu(x, out)
-    if out is None:
-        out = torch.empty_like(x)
+    out = _out_or_new(out, x, x.dtype, x.device, "scale")
     _native.check(lib.dd_scale(_ptr(x), _ptr(out), s, x.numel(), _dt(x), _stream()), "scale")
     return out
 
@@ -1071,8 +597,7 @@ def scale(x, s, out=None):
 def silu(x, out=None):
     lib = _native.load()
     _need_gpu(x, out)
-    if out is None:
-        out = torch.empty_like(x)
+    out = _out_or_new(out, x, x.dtype, x.device, "silu")
     _native.check(lib.dd_silu(_ptr(x), _ptr(out), x.numel(), _dt(x), _stream()), "silu")
     return out
 
@@ -1117,8 +642,7 @@ def timestep_embedding(t, dim, dtype, flip_sin_to_cos=True, freq_shift=0.0, out=
     if t.dtype != torch.float32:
         raise TypeError("timesteps must be fp32")
     n = t.numel()
-    if out is None:
-        out = torch.empty((n, dim), dtype=dtype, device=t.device)
+    out = _out_or_new(out, (n, dim), dtype if out is None else out.dtype, t.device, "timestep_embedding")
     rc = lib.dd_timestep_embedding(_ptr(t), _ptr(out), n, dim, int(flip_sin_to_cos), freq_shift,
                                    _dt(out), _stream())
     _native.check(rc, "timestep_embedding")
@@ -1131,8 +655,7 @@ def conv3x3_small_cout(x, w, bias, m, h, wd, out=None):
     _need_gpu(x, w, bias, out)
     cin = x.shape[1]
     cout = w.shape[0]
-    if out is None:
-        out = torch.empty((m, cout, h, wd), dtype=x.dtype, device=x.device)
+    out = _out_or_new(out, (m, cout, h, wd), x.dtype, x.device, "conv3x3_small_cout")
     rc = lib.dd_conv3x3_small_cout(_ptr(x), _ptr(w), _ptr(bias), _ptr(out), m, h, wd, cin, cout,
                                    _dt(x), _stream())
     _native.check(rc, "conv3x3_small_cout")
@@ -1234,8 +757,7 @@ def softmax_rows(s, dtype, pad_to=8):
     rows, cols = s.shape
     ldp = (cols + pad_to - 1) // pad_to * pad_to
     p = torch.empty((rows, ldp), dtype=dtype, device=s.device)
-    code = DD_F16 if dtype == torch.float16 else DD_BF16
-    _native.check(lib.dd_softmax_rows(_ptr(s), _ptr(p), rows, cols, s.stride(0), ldp, code, _stream()), "softmax_rows")
+    _native.check(lib.dd_softmax_rows(_ptr(s), _ptr(p), rows, cols, s.stride(0), ldp, _dtype_code(dtype), _stream()), "softmax_rows")
     return p
 
 
@@ -1253,16 +775,13 @@ def ors_project(occ, origin, direction, samples, step=0.2, *, want_labels=True, 
     n, hw = direction.shape[0], direction.shape[1]
     labels = torch.empty((n, hw, samples), dtype=torch.uint8, device=occ.device) if want_labels else None
     cond = torch.empty((n, samples, hw), dtype=cond_dtype, device=occ.device) if cond_dtype is not None else None
-    code = DD_F16 if cond_dtype in (None, torch.float16) else DD_BF16
     if cond_dtype not in (None, torch.float16, torch.bfloat16):
         raise TypeError("cond_dtype must be fp16 / bf16")
+    code = DD_F16 if cond_dtype is None else _dtype_code(cond_dtype)
     _native.check(lib.dd_ors_project(_ptr(occ), _ptr(origin), _ptr(direction), _ptr(labels), _ptr(cond), n, hw,
                                      int(samples), float(step), int(keep_fg), int(keep_bg), code, _stream()),
                   "ors_project")
     return labels, cond
-
-
-_FDT = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}
 
 
 def fourier_embed(x, freqs, include_input=True):
@@ -1406,11 +925,8 @@ def rowquant_fp8(x, norm=None):
     q = torch.empty((rows, kp), dtype=torch.uint8, device=x.device)
     scale = torch.empty(rows, dtype=torch.float32, device=x.device)
     g_, b_, eps_ = norm if norm is not None else (None, None, 0.0)
-    e0 = _TIMER.start() if _TIMER is not None else None
-    _native.check(lib.dd_rowquant_fp8(_ptr(x), _ptr(g_), _ptr(b_), _ptr(q), _ptr(scale), rows, c, kp, float(eps_), _dt(x),
-                                      _stream()), "rowquant_fp8")
-    if e0 is not None:
-        _TIMER.stop(e0, "dd_rowquant_fp8_kernel", 0.0, 2.0 * rows * c + rows * kp)
+    _timer.launch("rowquant_fp8", lib.dd_rowquant_fp8, _ptr(x), _ptr(g_), _ptr(b_), _ptr(q), _ptr(scale), rows, c, kp,
+                  float(eps_), _dt(x), _stream(), book=lambda: ("dd_rowquant_fp8_kernel", 0.0, 2.0 * rows * c + rows * kp))
     return q.view(torch.float8_e4m3fn), scale
 
 
@@ -1438,11 +954,7 @@ def gemm8(a8, a_scale, w8, w_scale, bias=None, *, res=None, out=None, head_major
         hm_out = torch.empty((n // hd, rows, hd), dtype=dtype, device=a8.device)
         out = hm_out.view(rows, n)
         d.out_headmajor_d, d.hm_scaled_planes, d.hm_scale = int(hd), int(hplanes), float(hscale)
-    if out is None:
-        out = torch.empty((rows, n // 2 if geglu else n), dtype=dtype, device=a8.device)
-    else:
-        _forget_derived(out)
-    out = _rows2d(out)
+    out = _rows2d(_out_or_new(out, (rows, n // 2 if geglu else n), dtype if out is None else out.dtype, a8.device, "gemm8"))
     d.a, d.a_scale, d.lda = a8.data_ptr(), a_scale.data_ptr(), a8.stride(0)
     d.w, d.w_scale, d.ldw = w8.data_ptr(), w_scale.data_ptr(), w8.stride(0)
     d.bias = bias.data_ptr() if bias is not None else None
@@ -1455,11 +967,9 @@ def gemm8(a8, a_scale, w8, w_scale, bias=None, *, res=None, out=None, head_major
         d.geglu = 1
     d.rows, d.n, d.k_padded = rows, n, a8.shape[1]
     d.dtype = _dt(out)
-    e0 = _TIMER.start() if _TIMER is not None else None
-    _native.check(lib.dd_gemm8(ctypes.byref(d), _stream()), "gemm8")
-    if e0 is not None:
-        _TIMER.stop(e0, "dd_gemm8_kernel", 2.0 * rows * n * a8.shape[1],
-                    1.0 * (rows + n) * a8.shape[1] + 2.0 * rows * n * (1 + (1 if res is not None else 0)))
+    _timer.launch("gemm8", lib.dd_gemm8, ctypes.byref(d), _stream(),
+                  book=lambda: ("dd_gemm8_kernel", 2.0 * rows * n * a8.shape[1],
+                                1.0 * (rows + n) * a8.shape[1] + 2.0 * rows * n * (1 + (1 if res is not None else 0))))
     return hm_out if hm_out is not None else out
 
 
@@ -1472,7 +982,7 @@ def gemm_kernel_name(rows, n, k, dtype=torch.bfloat16, conv=False, cin=0, hw=(0,
     d.rows, d.n, d.k, d.k1 = rows, n, k, k
     d.lda, d.ldc = k, n
     d.alpha = 1.0
-    d.dtype = DD_F16 if dtype == torch.float16 else DD_BF16
+    d.dtype = _dtype_code(dtype)
     if conv:
         d.conv = 1
         d.cin = cin; d.hin = d.hv = d.hout = hw[0]; d.win = d.wv = d.wout = hw[1]; d.stride = 1

@@ -2,13 +2,13 @@
 L2 / Infinity Cache before every launch, activations re-touched): python tools/cold_conv.py"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dualdiff_amd import ops as O
+from dualdiff_amd import ops as O, tuning
 M = 12; dt = torch.bfloat16; dev = torch.device("cuda:0")
 def r(*shape, s=1.0): return (torch.randn(*shape, device="cuda") * s).to(dt)
 def cold(fn, warm, n=5):
     tot = 0.0
     for _ in range(n):
-        O._flush_and_warm(dev, warm)
+        tuning._flush_and_warm(dev, warm)
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
         e0.record(); fn(); e1.record(); e1.synchronize()
         tot += e0.elapsed_time(e1)

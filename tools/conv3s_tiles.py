@@ -1,13 +1,13 @@
 """Cold-weight timing of the deep-level conv shapes over the conv3s tiles x split-K."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dualdiff_amd import ops as O
+from dualdiff_amd import ops as O, tuning
 M = 12; dt = torch.bfloat16; dev = torch.device("cuda:0")
 def r(*shape, s=1.0): return (torch.randn(*shape, device="cuda") * s).to(dt)
 def cold(fn, warm, n=5):
     ts = []
     for _ in range(n):
-        O._flush_and_warm(dev, warm)
+        tuning._flush_and_warm(dev, warm)
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
         e0.record(); fn(); e1.record(); e1.synchronize()
         ts.append(e0.elapsed_time(e1) * 1e3)
