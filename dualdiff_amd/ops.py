@@ -320,6 +320,86 @@ def vae_posterior(moments, wq, bq, m, h, w, noise=None, scale=1.0, out_f32=False
     return z
 
 
+def _image_arg(x, what):
+    if x.dim() != 4 or x.shape[1] != 3 or x.numel() == 0:
+        raise ValueError("%s takes an (m, 3, h, w) image batch, got %s" % (what, tuple(x.shape)))
+    if x.dtype not in _FDT:
+        raise ValueError("%s takes fp16 / bf16 / fp32 images, got %s" % (what, x.dtype))
+    if not x.is_contiguous():
+        raise ValueError("%s takes a contiguous NCHW tensor" % what)
+    return x.shape[0], x.shape[2], x.shape[3]
+
+
+def _image_out(out, shape, device, what):
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError("%s: out must be a contiguous uint8 %s tensor" % (what, tuple(shape)))
+    return out
+
+
+def image_padding(padding):
+    """torchvision.transforms.Pad's forms -> (left, top, right, bottom): an int (every side), a pair (left / right, top /
+    bottom) or the four sides."""
+    if isinstance(padding, int) and not isinstance(padding, bool):
+        p = (padding,) * 4
+    else:
+        try:
+            p = tuple(padding)
+        except TypeError:
+            raise ValueError("padding must be an int or a sequence of 2 or 4 ints, got %r" % (padding,))
+        if len(p) == 1:
+            p = p * 4
+        elif len(p) == 2:
+            p = (p[0], p[1], p[0], p[1])
+    if len(p) != 4 or any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in p):
+        raise ValueError("padding must be an int or a sequence of 2 or 4 non-negative ints, got %r" % (padding,))
+    return p
+
+
+def image_quantize_u8(x, m11=False, out=None):
+    """(m, 3, h, w) images in [0, 1] (fp16 / bf16 / fp32) -> (m, h, w, 3) uint8, `(x.float().numpy() * 255).round()
+    .astype("uint8")` of diffusers' numpy_to_pil behind a clamp (dd_image_quantize_u8).  m11: x is a decoder output in
+    [-1, 1] and goes through decode_latents' `clamp(x / 2 + 0.5, 0, 1)` first."""
+    m, h, w = _image_arg(x, "image_quantize_u8")
+    out = _image_out(out, (m, h, w, 3), x.device, "image_quantize_u8")
+    _need_gpu(x, out)
+    lib = _native.load()
+    _timer.launch("image_quantize_u8", lib.dd_image_quantize_u8, _ptr(x), _ptr(out), m, h, w, int(bool(m11)),
+                  _FDT[x.dtype], _stream(),
+                  book=lambda: ("dd_image_quantize_kernel", 0.0, float(x.numel() * x.element_size() + out.numel())))
+    return out
+
+
+def image_resample_u8(x, size, padding=(0, 0, 0, 0), fill=0, m11=False, out=None):
+    """PIL's `Image.resize(size[::-1], BICUBIC)` and torchvision's `Pad(padding, fill)` of the quantised images, byte for
+    byte and in one launch (dd_image_resample_u8): x (m, 3, h, w) as image_quantize_u8 takes it, size = (h, w) of the
+    resize, padding = (left, top, right, bottom) or Pad's shorter forms -> (m, top + h + bottom, left + w + right, 3)
+    uint8.  The coefficient tables are built on the host once per size pair and kept per device
+    (pipeline.image_output.device_tables): call once before capturing the launch in a graph."""
+    m, h, w = _image_arg(x, "image_resample_u8")
+    try:
+        oh, ow = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError("size must be (h, w), got %r" % (size,))
+    if oh <= 0 or ow <= 0:
+        raise ValueError("size must be positive, got %r" % (size,))
+    pl, pt, pr, pb = image_padding(padding)
+    if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 255:
+        raise ValueError("fill must be a byte value, got %r" % (fill,))
+    out = _image_out(out, (m, pt + oh + pb, pl + ow + pr, 3), x.device, "image_resample_u8")
+    _need_gpu(x, out)
+    lib = _native.load()
+    from .pipeline.image_output import device_tables
+    kx, bx = device_tables(w, ow, x.device)
+    ky, by = device_tables(h, oh, x.device)
+    _timer.launch("image_resample_u8", lib.dd_image_resample_u8, _ptr(x), _ptr(out), m, h, w, oh, ow, _ptr(kx), _ptr(bx),
+                  kx.shape[1], _ptr(ky), _ptr(by), ky.shape[1], pl, pt, pr, pb, fill, int(bool(m11)), _FDT[x.dtype],
+                  _stream(),
+                  book=lambda: ("dd_image_resample_kernel", 0.0, float(x.numel() * x.element_size() + out.numel())))
+    return out
+
+
 def groupnorm(x, gamma, beta, m, hw, groups, eps, silu, x2=None, out=None):
     """GroupNorm (+SiLU) over an NHWC batch; x2 = optional second source concatenated on C."""
     lib = _native.load()

@@ -430,6 +430,48 @@ int dd_vae_posterior(const void* moments, const float* wq, const float* bq, cons
                      int32_t m, int32_t h, int32_t w, float scale, int32_t out_f32, int32_t dtype, dd_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Image output (csrc/image.hip): what the reference does to the decoded images before it saves them — the host copy
+ * and diffusers' numpy_to_pil, `(images * 255).round().astype("uint8")` (pipeline/pipeline_bev_controlnet.py:112,540,
+ * numpy_to_pil_double :72-80), then per view torchvision's Resize(cfg.fid.resize, BICUBIC) and Pad(cfg.fid.padding) on
+ * the PIL image (perception/data_prepare/val_set_gen.py:147-159, applied at :44).
+ * ------------------------------------------------------------------------- */
+/* x: NCHW (m, 3, h, w) in `dtype` (DD_F16, DD_BF16 or DD_F32), contiguous -> out: NHWC (m, h, w, 3) bytes,
+ *   v = m11 ? clamp(float(x) / 2 + 0.5, 0, 1) : clamp(float(x), 0, 1)     (m11: a decoder output in [-1, 1], the
+ *                                                                           arithmetic of decode_latents, :110-111)
+ *   q = (uint8) rint(v * 255)          one fp32 multiply, round to nearest even (numpy's round)
+ * out needs no alignment (dword stores where an image's first byte is 4-byte aligned, byte stores otherwise).
+ * m <= 65535 and h * w < 2^31, else DD_ERR_UNSUPPORTED. */
+int dd_image_quantize_u8(const void* x, uint8_t* out, int32_t m, int32_t h, int32_t w, int32_t m11, int32_t dtype,
+                         dd_stream_t stream);
+
+/* PIL's Image.resize(BICUBIC) of the quantised image (ImagingResample on 8-bit pixels: two passes of integer
+ * arithmetic over fixed-point coefficient tables) followed by Pad, in one launch and without the uint8 input image:
+ *   q                = the bytes dd_image_quantize_u8 would write for x
+ *   t[r, X, c]       = clamp8( ((1 << 21) + sum_{j < bx[X].count} q[r, bx[X].xmin + j, c] * kx[X][j]) >> 22 )
+ *   out[Y, X, c]     = clamp8( ((1 << 21) + sum_{j < by[Y].count} t[by[Y].xmin + j, X, c] * ky[Y][j]) >> 22 )
+ * in int32 with an arithmetic shift, clamp8 = clamp to [0, 255]; t is rounded and clipped to a byte between the
+ * passes, as PIL does.  The (oh, ow) result sits at (pad_t, pad_l) of out, (m, pad_t + oh + pad_b, pad_l + ow + pad_r,
+ * 3) bytes; every other pixel of out is `fill`.  out needs no alignment.
+ * Tables (device memory, int32): kx [ow][ksx], bx [ow][2] = {xmin, count}; ky [oh][ksy], by [oh][2].  They are PIL's
+ * precompute_coeffs + normalize_coeffs_8bpc, built by the caller in float64 (dualdiff_amd/pipeline/image_output.py:
+ * resample_tables): scale = in / out, fs = max(scale, 1), support = 2 fs, ksize = 2 ceil(support) + 1; for output xx:
+ * c = (xx + 0.5) scale, xmin = max(int(c - support + 0.5), 0), count = min(int(c + support + 0.5), in) - xmin,
+ * w[x] = bicubic((x + xmin - c + 0.5) / fs) with a = -0.5, normalised by their left-to-right sum, then
+ * k = int(w * 2^22 +- 0.5) (towards the sign of w), zero after `count`.  An axis that keeps its size takes the one-tap
+ * table {k = 1 << 22, xmin = xx, count = 1} (PIL skips that pass; the bytes are the same).
+ * A workgroup owns an output tile and keeps its slice of t in LDS; the slice is sized for PIL's tables, whose T
+ * consecutive outputs read at most ceil((T - 1) in / out) + ksize + 1 inputs.  Entries of other tables are clamped to
+ * the image and to that slice: the result is then unspecified, nothing outside the buffers is touched.
+ * 1 <= ksx, ksy <= DD_IMAGE_MAX_KSIZE (in / out up to 8; a tile that does not fit 64 KB of LDS at the smallest tile
+ * size), m <= 65535: else DD_ERR_UNSUPPORTED.  NULL pointers, non-positive sizes, negative pads, fill outside [0, 255]:
+ * DD_ERR_BAD_ARG.  Both are decided before anything is launched. */
+#define DD_IMAGE_MAX_KSIZE 33
+int dd_image_resample_u8(const void* x, uint8_t* out, int32_t m, int32_t h, int32_t w, int32_t oh, int32_t ow,
+                         const int32_t* kx, const int32_t* bx, int32_t ksx, const int32_t* ky, const int32_t* by,
+                         int32_t ksy, int32_t pad_l, int32_t pad_t, int32_t pad_r, int32_t pad_b, int32_t fill,
+                         int32_t m11, int32_t dtype, dd_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * CLIP text encoder (csrc/clip.hip): the SD-v1.5 `text_encoder` (transformers.CLIPTextModel) that the reference calls at
  * runner/base_runner.py:119,511-514, runner/multiview_runner.py:145,427-428 (`text_encoder(ids)[0]`), through diffusers'
  * _encode_prompt at pipeline/pipeline_bev_controlnet.py:273 and at networks/bbox_embedder.py:133-145
