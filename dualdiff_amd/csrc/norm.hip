@@ -545,6 +545,16 @@ bool launch_layernorm_sub(const void* x, const void* gamma, const void* beta, vo
   }
 }
 
+// Both GroupNorm forms split a 16-B vector (8 channels starting at a multiple of 8) between the group of its first
+// channel and ONE other group.  That holds when every such vector touches at most two groups: 4 channels per group
+// (two whole groups) and 6 or more do; 1, 2, 3 and 5 do not (cpg = 5: channels 8..15 lie in groups 1, 2 and 3).
+bool gn_vector_in_two_groups(int cpg) {
+  if (cpg >= 8) return true;                          // a vector is no longer than a group
+  for (int ch = 0; ch < 8 * cpg; ch += 8)             // every offset of a vector start inside a group
+    if ((ch + 7) / cpg - ch / cpg > 1) return false;
+  return true;
+}
+
 int gn_plan(int hw, int c, int* pix_per_split) {
   // enough blocks to fill the chip, but at least a few pixels per pixel-lane
   const int cv = c / 8;
@@ -574,7 +584,7 @@ extern "C" int dd_groupnorm_nhwc(const void* x1, int32_t c1, const void* x2, int
   const int c = c1 + c2;
   if (m <= 0 || hw <= 0 || groups <= 0 || groups > 64 || c1 <= 0) return DD_ERR_BAD_ARG;
   if ((c1 & 7) || (c2 & 7) || c % groups != 0 || c > GN_MAX_C) return DD_ERR_BAD_ARG;
-  if (c / groups < 4) return DD_ERR_UNSUPPORTED;   // a 16-B vector may span at most 2 groups (4 channels each at least)
+  if (!gn_vector_in_two_groups(c / groups)) return DD_ERR_UNSUPPORTED;   // 1, 2, 3 or 5 channels per group
   if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
   if (!dd_aligned16(x1) || (x2 && !dd_aligned16(x2)) || !dd_aligned16(y) ||
       !dd_aligned16(gamma) || !dd_aligned16(beta)) return DD_ERR_BAD_ARG;
@@ -616,7 +626,7 @@ extern "C" int dd_groupnorm_splitk(const float* partial, int32_t nsplit, const v
                                    int32_t groups, float eps, int32_t apply_silu, int32_t dtype, dd_stream_t stream) {
   if (!partial || !gamma || !beta || !y || nsplit < 2 || nsplit > 64) return DD_ERR_BAD_ARG;
   if (m <= 0 || hw <= 0 || groups <= 0 || groups > 64 || c <= 0 || (c & 7) || c % groups || c > GN_MAX_C) return DD_ERR_BAD_ARG;
-  if (c / groups < 4) return DD_ERR_UNSUPPORTED;
+  if (!gn_vector_in_two_groups(c / groups)) return DD_ERR_UNSUPPORTED;
   if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
   if (!dd_aligned16(partial) || !dd_aligned16(y) || !dd_aligned16(gamma) || !dd_aligned16(beta) ||
       (bias && !dd_aligned16(bias)) || (rowvec && (!dd_aligned16(rowvec) || (ld_rowvec & 7))) ||
@@ -644,7 +654,7 @@ extern "C" int dd_groupnorm_splitk(const float* partial, int32_t nsplit, const v
 
 extern "C" int dd_groupnorm_is_fused(int32_t hw, int32_t c, int32_t groups) {
   int cpb, vpp, plc, nv, kred, threads;
-  if (hw <= 0 || c <= 0 || groups <= 0 || c % groups) return 0;
+  if (hw <= 0 || c <= 0 || groups <= 0 || c % groups || !gn_vector_in_two_groups(c / groups)) return 0;
   return gn_fused_plan(hw, c, groups, &cpb, &vpp, &plc, &nv, &kred, &threads) ? threads : 0;
 }
 

@@ -198,7 +198,9 @@ const char* dd_gemm_conv_pad_kernel_name(const dd_gemm_desc* d, int32_t pad_lo);
  * Transformer2DModel input norm (eps 1e-6, no SiLU) and conv_norm_out
  * (networks/unet_2d_condition_multiview.py:519-522).
  * ws: fp32 scratch, >= dd_groupnorm_workspace_bytes(M, G), private to the stream (first 256 bytes reserved).
- * C1 + C2 = C, C % G == 0, C1 % 8 == 0, C2 % 8 == 0.
+ * C1 + C2 = C, C % G == 0, C1 % 8 == 0, C2 % 8 == 0, C <= 4096, G <= 64.
+ * A 16-byte vector (8 channels from a multiple of 8) must touch at most two groups: C / G = 4 or >= 6; 1, 2, 3 and 5
+ * channels per group are DD_ERR_UNSUPPORTED (also from dd_groupnorm_splitk; dd_groupnorm_is_fused reports 0).
  * ------------------------------------------------------------------------- */
 int dd_groupnorm_nhwc(const void* x1, int32_t c1, const void* x2, int32_t c2,
                       const void* gamma, const void* beta, void* y,
