@@ -4,6 +4,7 @@
 //    (pipeline/pipeline_bev_controlnet.py:112,540; numpy_to_pil_double :72-80).
 //  * dd_image_resample_u8: the same quantisation on load, then PIL's Image.resize(BICUBIC) on 8-bit pixels and
 //    torchvision's Pad (perception/data_prepare/val_set_gen.py:147-159), one launch, byte for byte.
+// Image input, further down: dd_image_load_u8, uint8 camera frames to the normalised pixel values the VAE encoder takes.
 //
 // PIL resamples 8-bit images in integer arithmetic: per output coordinate a row of 22-bit fixed-point coefficients and
 // the window {xmin, count} it applies to; a horizontal pass over every input row, rounded and clipped to a byte, then a
@@ -230,6 +231,167 @@ static inline int cap_of(int tile, int in, int out, int ks) {
   return (int)(span < in ? span : in);
 }
 
+// ---- image input: uint8 HWC frames -> normalised float pixel values --------------------------------------------------
+//
+// dd_image_load_u8 is the resample the other way round: the input is already pixel-interleaved bytes, so staging the
+// window is a copy (aligned dwords of every row segment, bytes at its ends; a row keeps its global address mod 4 in LDS so
+// that the dwords stay aligned on both sides), the two passes are the ones above, and the vertical pass of a pixel ends in
+// three look-ups of the caller's float[3][256] table and goes straight to global memory: one element per channel plane
+// with lanes along x (layout 0), or the pixel's 8 channels-last elements as 16-byte stores (layout 1).  A crop is a slice
+// of the tables, so a workgroup's tile is a tile of the crop and nothing outside it is staged or computed.
+
+struct LoadArgs {
+  const uint8_t* in;
+  void* out;
+  const int32_t *kx, *bx, *ky, *by;
+  const float* lut;
+  int32_t h, w, oh, ow, ksx, ksy;
+  int32_t tw, th;                            // tile of the output, pixels; tw % 4 == 0
+  int32_t capw, caph;                        // input columns / rows the LDS slice holds
+  int32_t qp;                                // pitch of the input window, bytes (multiple of 4, >= capw * 3 + 3)
+};
+
+// LDS image of a workgroup, in this order (every part a multiple of 4 bytes):
+//   int32 lkx[tw * ksx], lbx[tw * 2], lky[th * ksy], lby[th * 2]   as in dd_image_resample_kernel
+//   float llut[3 * 256]                                             the normalisation table
+//   uint8 t[caph][tw * 3]                                           horizontal pass, tile byte columns
+//   uint8 q[caph][qp]                                               input window; row r starts at byte (its address & 3)
+static inline size_t load_lds_bytes(int tw, int th, int ksx, int ksy, int capw, int caph, int* qp) {
+  *qp = (capw * 3 + 3 + 3) & ~3;
+  return (size_t)4 * (tw * ksx + tw * 2 + th * ksy + th * 2 + 768) + (size_t)caph * tw * 3 + (size_t)caph * *qp;
+}
+
+// The kernel sees a slice of the tables and not the size of the resized image, so the slice is sized from ksize alone:
+// ksize = 2 ceil(2 max(in / out, 1)) + 1 gives in / out <= max(ksize - 1, 4) / 4, and with it PIL's bound of cap_of.  The
+// image's own size does not enter, so that a small image takes the tile a large one takes at the same ratio.
+static inline int load_cap_of(int tile, int ks) {
+  const int num = ks - 1 > 4 ? ks - 1 : 4;
+  return ((tile - 1) * num + 3) / 4 + ks + 1;
+}
+
+template <typename T, int LAYOUT>
+__global__ __launch_bounds__(kThreads)
+void dd_image_load_kernel(const LoadArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t dd_img_lds[];
+  const int tid = threadIdx.x;
+  const int tw = a.tw, th = a.th, ksx = a.ksx, ksy = a.ksy;
+  const int X0 = blockIdx.x * tw, Y0 = blockIdx.y * th;
+  const int64_t img = blockIdx.z;
+  const int ncol = min(tw, a.ow - X0), nrow = min(th, a.oh - Y0);           // >= 1 by the grid
+
+  int32_t* lkx = reinterpret_cast<int32_t*>(dd_img_lds);
+  int32_t* lbx = lkx + tw * ksx;
+  int32_t* lky = lbx + tw * 2;
+  int32_t* lby = lky + th * ksy;
+  float* llut = reinterpret_cast<float*>(lby + th * 2);
+  const int tp = tw * 3, qp = a.qp;
+  uint8_t* t = reinterpret_cast<uint8_t*>(llut + 768);
+  uint8_t* q = t + a.caph * tp;
+
+  // the input window of the tile: columns [c0, c0 + nc), rows [r0, r0 + nr)
+  const int c0 = dd_clampi(a.bx[2 * X0], 0, a.w);
+  const int ce = dd_clampi(a.bx[2 * (X0 + ncol - 1)], 0, a.w) + dd_clampi(a.bx[2 * (X0 + ncol - 1) + 1], 0, ksx);
+  const int nc = dd_clampi(min(ce, a.w) - c0, 0, a.capw);
+  const int r0 = dd_clampi(a.by[2 * Y0], 0, a.h);
+  const int re = dd_clampi(a.by[2 * (Y0 + nrow - 1)], 0, a.h) + dd_clampi(a.by[2 * (Y0 + nrow - 1) + 1], 0, ksy);
+  const int nr = dd_clampi(min(re, a.h) - r0, 0, a.caph);
+  // the tables of the tile; windows clamped to the slice, so that no table can index outside it
+  for (int i = tid; i < ncol; i += kThreads) {
+    const int rel = dd_clampi(dd_clampi(a.bx[2 * (X0 + i)], 0, a.w) - c0, 0, nc);
+    lbx[2 * i] = rel;
+    lbx[2 * i + 1] = min(dd_clampi(a.bx[2 * (X0 + i) + 1], 0, ksx), nc - rel);
+  }
+  for (int i = tid; i < ncol * ksx; i += kThreads) lkx[i] = a.kx[(int64_t)X0 * ksx + i];
+  for (int i = tid; i < nrow; i += kThreads) {
+    const int rel = dd_clampi(dd_clampi(a.by[2 * (Y0 + i)], 0, a.h) - r0, 0, nr);
+    lby[2 * i] = rel;
+    lby[2 * i + 1] = min(dd_clampi(a.by[2 * (Y0 + i) + 1], 0, ksy), nr - rel);
+  }
+  for (int i = tid; i < nrow * ksy; i += kThreads) lky[i] = a.ky[(int64_t)Y0 * ksy + i];
+  for (int i = tid; i < 768; i += kThreads) llut[i] = a.lut[i];
+  // copy the window: per row the segment [g, g + nb); slot s is the aligned dword at g - mis + 4 s, kept at q + 4 s
+  const int64_t rowb = (int64_t)a.w * 3;
+  const uint8_t* src = a.in + ((img * a.h + r0) * a.w + c0) * 3;
+  const int nb = nc * 3;
+  const int slots = ((nb + 3) >> 2) + 1;
+  for (int i = tid; i < nr * slots; i += kThreads) {
+    const int s = i % slots, r = i / slots;
+    const uint8_t* g = src + r * rowb;
+    const int mis = (int)(reinterpret_cast<uintptr_t>(g) & 3u);
+    const int off = 4 * s - mis;                              // segment byte of the dword's first byte
+    uint8_t* qrow = q + r * qp + mis;                         // where segment byte 0 goes
+    if (off >= 0 && off + 4 <= nb) {
+      *reinterpret_cast<uint32_t*>(qrow + off) = *reinterpret_cast<const uint32_t*>(g + off);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (off + k >= 0 && off + k < nb) qrow[off + k] = g[off + k];
+    }
+  }
+  __syncthreads();
+
+  // horizontal pass: one (input row, output column) per lane, three channels share the coefficient loads
+  for (int i = tid; i < nr * ncol; i += kThreads) {
+    const int oc = i % ncol, r = i / ncol;
+    const int rel = lbx[2 * oc], cnt = lbx[2 * oc + 1];
+    const int32_t* kk = lkx + oc * ksx;
+    const int mis = (int)(reinterpret_cast<uintptr_t>(src + r * rowb) & 3u);
+    const uint8_t* p = q + r * qp + mis + rel * 3;
+    int32_t a0 = 1 << (kPB - 1), a1 = a0, a2 = a0;
+    for (int j = 0; j < cnt; ++j) {
+      const int32_t k = kk[j];
+      a0 += (int32_t)p[3 * j] * k;
+      a1 += (int32_t)p[3 * j + 1] * k;
+      a2 += (int32_t)p[3 * j + 2] * k;
+    }
+    uint8_t* d = t + r * tp + oc * 3;
+    d[0] = (uint8_t)dd_clip8(a0);
+    d[1] = (uint8_t)dd_clip8(a1);
+    d[2] = (uint8_t)dd_clip8(a2);
+  }
+  __syncthreads();
+
+  // vertical pass: one pixel per lane, lanes along x; the three bytes index the table and go out in T
+  for (int i = tid; i < nrow * tw; i += kThreads) {
+    const int x = i % tw, y = i / tw;
+    if (x >= ncol) continue;
+    const int rel = lby[2 * y], cnt = lby[2 * y + 1];
+    const int32_t* kk = lky + y * ksy;
+    const uint8_t* p = t + rel * tp + x * 3;
+    int32_t a0 = 1 << (kPB - 1), a1 = a0, a2 = a0;
+    for (int j = 0; j < cnt; ++j) {
+      const int32_t k = kk[j];
+      a0 += (int32_t)p[j * tp] * k;
+      a1 += (int32_t)p[j * tp + 1] * k;
+      a2 += (int32_t)p[j * tp + 2] * k;
+    }
+    const T v0 = (T)llut[dd_clip8(a0)], v1 = (T)llut[256 + dd_clip8(a1)], v2 = (T)llut[512 + dd_clip8(a2)];
+    if (LAYOUT == 0) {
+      const int64_t plane = (int64_t)a.oh * a.ow;
+      T* o = reinterpret_cast<T*>(a.out) + img * 3 * plane + (int64_t)(Y0 + y) * a.ow + X0 + x;
+      o[0] = v0;
+      o[plane] = v1;
+      o[2 * plane] = v2;
+    } else {
+      const T zero = (T)0.0f;
+      const T px[8] = {v0, v1, v2, zero, zero, zero, zero, zero};
+      u32x4 u[sizeof(T) / 2];
+      __builtin_memcpy(u, px, sizeof(px));
+      uint8_t* o = reinterpret_cast<uint8_t*>(a.out) + ((img * a.oh + Y0 + y) * a.ow + X0 + x) * (int64_t)sizeof(px);
+#pragma unroll
+      for (int k = 0; k < (int)(sizeof(T) / 2); ++k) dd_st16(o + 16 * k, u[k]);
+    }
+  }
+}
+
+template <typename T>
+static inline void launch_load(const LoadArgs& a, int layout, dim3 grid, size_t lds, hipStream_t s) {
+  if (layout == 0)
+    hipLaunchKernelGGL((dd_image_load_kernel<T, 0>), grid, dim3(kThreads), lds, s, a);
+  else
+    hipLaunchKernelGGL((dd_image_load_kernel<T, 1>), grid, dim3(kThreads), lds, s, a);
+}
+
 }  // namespace
 
 extern "C" int dd_image_quantize_u8(const void* x, uint8_t* out, int32_t m, int32_t h, int32_t w, int32_t m11,
@@ -286,5 +448,42 @@ extern "C" int dd_image_resample_u8(const void* x, uint8_t* out, int32_t m, int3
     hipLaunchKernelGGL(dd_image_resample_kernel<__bf16>, grid, dim3(kThreads), lds, s, a);
   else
     hipLaunchKernelGGL(dd_image_resample_kernel<float>, grid, dim3(kThreads), lds, s, a);
+  return dd_check_launch();
+}
+
+extern "C" int dd_image_load_u8(const uint8_t* in, void* out, int32_t m, int32_t h, int32_t w, int32_t oh, int32_t ow,
+                                const int32_t* kx, const int32_t* bx, int32_t ksx, const int32_t* ky, const int32_t* by,
+                                int32_t ksy, const float* lut, int32_t dtype, int32_t layout, dd_stream_t stream) {
+  if (!in || !out || !kx || !bx || !ky || !by || !lut) return DD_ERR_BAD_ARG;
+  if (m <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0 || ksx <= 0 || ksy <= 0) return DD_ERR_BAD_ARG;
+  if (dtype != DD_F16 && dtype != DD_BF16 && dtype != DD_F32) return DD_ERR_BAD_ARG;
+  if (layout != 0 && layout != 1) return DD_ERR_BAD_ARG;
+  if (layout == 1 && !dd_aligned16(out)) return DD_ERR_BAD_ARG;
+  if (ksx > DD_IMAGE_MAX_KSIZE || ksy > DD_IMAGE_MAX_KSIZE || m > 65535) return DD_ERR_UNSUPPORTED;
+  if (oh >= (1 << 24) || ow >= (1 << 24) || h >= (1 << 24) || w >= (1 << 24)) return DD_ERR_UNSUPPORTED;
+  LoadArgs a;
+  a.in = in; a.out = out; a.kx = kx; a.bx = bx; a.ky = ky; a.by = by; a.lut = lut;
+  a.h = h; a.w = w; a.oh = oh; a.ow = ow; a.ksx = ksx; a.ksy = ksy;
+  size_t lds = 0;
+  bool found = false;
+  for (const auto& tile : kTiles) {
+    a.tw = tile[0]; a.th = tile[1];
+    a.capw = load_cap_of(a.tw, ksx);
+    a.caph = load_cap_of(a.th, ksy);
+    lds = load_lds_bytes(a.tw, a.th, ksx, ksy, a.capw, a.caph, &a.qp);
+    if (lds <= 65536) { found = true; break; }
+  }
+  if (!found) return DD_ERR_UNSUPPORTED;
+  const int64_t gx = ((int64_t)ow + a.tw - 1) / a.tw, gy = ((int64_t)oh + a.th - 1) / a.th;
+  if (gy > 65535) return DD_ERR_UNSUPPORTED;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)m);
+  dd_clear_error();
+  if (dtype == DD_F16)
+    launch_load<_Float16>(a, layout, grid, lds, s);
+  else if (dtype == DD_BF16)
+    launch_load<__bf16>(a, layout, grid, lds, s);
+  else
+    launch_load<float>(a, layout, grid, lds, s);
   return dd_check_launch();
 }

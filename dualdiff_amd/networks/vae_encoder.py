@@ -141,8 +141,21 @@ class AutoencoderKLEncoder(nn.Module):
             raise ValueError("image height and width must be multiples of 8, got %d x %d" % (h, w))
         if not x.is_cuda:
             raise RuntimeError("the VAE encoder runs on the GPU only")
-        enc = self.encoder
         x8 = O.nchw_to_nhwc(x.to(self.dtype).contiguous(), 8)          # (m*h*w, 8), channels 3..7 zero
+        return self.encode_nhwc8(x8, m, h, w)
+
+    @torch.no_grad()
+    def encode_nhwc8(self, x8, m, h, w):
+        """The encoder behind `nchw_to_nhwc(x, 8)`: x8 (m*h*w, 8) channels-last rows in the model dtype, channels 3..7
+        zero — what `ops.image_load_u8(..., layout="nhwc8")` writes — -> EncoderOutput."""
+        if x8.dim() != 2 or tuple(x8.shape) != (m * h * w, 8) or x8.dtype != self.dtype or not x8.is_contiguous():
+            raise ValueError("encode_nhwc8 takes a contiguous (%d, 8) %s tensor, got %s %s"
+                             % (m * h * w, self.dtype, tuple(x8.shape), x8.dtype))
+        if h % 8 or w % 8:
+            raise ValueError("image height and width must be multiples of 8, got %d x %d" % (h, w))
+        if not x8.is_cuda:
+            raise RuntimeError("the VAE encoder runs on the GPU only")
+        enc = self.encoder
         x = enc.conv_in.run(x8, m, h, w)
         for blk in enc.down_blocks:
             x, h, w = blk.run(x, m, h, w)

@@ -400,6 +400,96 @@ def image_resample_u8(x, size, padding=(0, 0, 0, 0), fill=0, m11=False, out=None
     return out
 
 
+_IMAGE_LUTS = {}                # (mean, std, device) -> float32 (3, 256) on the device
+_IMAGE_LAYOUTS = {"nchw": 0, "nhwc8": 1}
+
+
+def _image_mean_std(mean, std):
+    try:
+        mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+    except (TypeError, ValueError):
+        raise ValueError("mean and std must be 3 numbers each, got %r / %r" % (mean, std))
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("mean and std must be 3 numbers each, got %r / %r" % (mean, std))
+    if any(v == 0 for v in std):
+        raise ValueError("std must not be 0 (Normalize would divide by zero), got %r" % (std,))
+    return mean, std
+
+
+def image_norm_lut(mean, std):
+    """torchvision's ToTensor + Normalize on every byte value, with torch's own float32 ops: (3, 256) float32 on the host,
+    lut[c, b] = (b / 255 - mean[c]) / std[c]."""
+    mean, std = _image_mean_std(mean, std)
+    x = torch.arange(256).float().div(255)                   # ToTensor
+    mean, std = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
+    return x[None].sub(mean[:, None]).div(std[:, None]).contiguous()      # Normalize: float32 tensors, as torchvision's
+
+
+def _image_lut(mean, std, device):
+    key = (mean, std, device.type,
+           device.index if device.index is not None else torch.cuda.current_device())
+    if key not in _IMAGE_LUTS:
+        _IMAGE_LUTS[key] = image_norm_lut(mean, std).to(device)
+    return _IMAGE_LUTS[key]
+
+
+def image_load_u8(frames, size, box=None, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), dtype=torch.float32, layout="nchw",
+                  out=None):
+    """uint8 frames (m, h, w, 3) -> normalised pixel values, the dataset transform `ToTensor` / `Normalize(mean, std)` of
+    `pil.resize(size[::-1], BICUBIC).crop(box)` element for element and in one launch (dd_image_load_u8): size = (h, w)
+    of the resize, box = PIL's (left, top, right, bottom) inside the resized image (default: all of it), dtype fp16 /
+    bf16 / fp32.  layout "nchw" -> (m, 3, bottom - top, right - left); "nhwc8" -> (m * rows * cols, 8) channels-last
+    with channels 3..7 zero, what `nchw_to_nhwc(x, 8)` hands to the VAE encoder's conv_in.  Only the crop is computed.
+    The coefficient tables and the normalisation table are built on the host once per size pair / (mean, std) and kept
+    per device: call once before capturing the launch in a graph."""
+    what = "image_load_u8"
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
+        raise ValueError("%s takes an (m, h, w, 3) frame batch, got %s" % (what, tuple(frames.shape)))
+    if frames.dtype != torch.uint8:
+        raise ValueError("%s takes uint8 frames, got %s" % (what, frames.dtype))
+    if not frames.is_contiguous():
+        raise ValueError("%s takes a contiguous NHWC tensor" % what)
+    m, h, w = frames.shape[0], frames.shape[1], frames.shape[2]
+    try:
+        nh, nw = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError("size must be (h, w), got %r" % (size,))
+    if nh <= 0 or nw <= 0:
+        raise ValueError("size must be positive, got %r" % (size,))
+    if box is None:
+        box = (0, 0, nw, nh)
+    try:
+        left, top, right, bottom = (int(v) for v in box)
+    except (TypeError, ValueError):
+        raise ValueError("box must be (left, top, right, bottom), got %r" % (box,))
+    if not (0 <= left < right <= nw and 0 <= top < bottom <= nh):
+        raise ValueError("box %r is empty or leaves the %d x %d (w x h) resized image" % (tuple(box), nw, nh))
+    if layout not in _IMAGE_LAYOUTS:
+        raise ValueError("layout must be one of %s, got %r" % (", ".join(sorted(_IMAGE_LAYOUTS)), layout))
+    if dtype not in _FDT:
+        raise ValueError("%s writes fp16 / bf16 / fp32, got %s" % (what, dtype))
+    mean, std = _image_mean_std(mean, std)
+    oh, ow = bottom - top, right - left
+    shape = (m, 3, oh, ow) if layout == "nchw" else (m * oh * ow, 8)
+    if out is None:
+        _need_gpu(frames)
+        out = torch.empty(shape, dtype=dtype, device=frames.device)
+    elif out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError("%s: out must be a contiguous %s %s tensor" % (what, dtype, shape))
+    _need_gpu(frames, out)
+    _forget_derived(out)
+    lib = _native.load()
+    from .pipeline.image_output import device_tables
+    kx, bx = device_tables(w, nw, frames.device)
+    ky, by = device_tables(h, nh, frames.device)
+    lut = _image_lut(mean, std, frames.device)
+    _timer.launch(what, lib.dd_image_load_u8, _ptr(frames), _ptr(out), m, h, w, oh, ow, _ptr(kx[left:]), _ptr(bx[left:]),
+                  kx.shape[1], _ptr(ky[top:]), _ptr(by[top:]), ky.shape[1], _ptr(lut), _FDT[dtype],
+                  _IMAGE_LAYOUTS[layout], _stream(),
+                  book=lambda: ("dd_image_load_kernel", 0.0, float(frames.numel() + out.numel() * out.element_size())))
+    return out
+
+
 def groupnorm(x, gamma, beta, m, hw, groups, eps, silu, x2=None, out=None):
     """GroupNorm (+SiLU) over an NHWC batch; x2 = optional second source concatenated on C."""
     lib = _native.load()

@@ -473,6 +473,32 @@ int dd_image_resample_u8(const void* x, uint8_t* out, int32_t m, int32_t h, int3
                          int32_t ksy, int32_t pad_l, int32_t pad_t, int32_t pad_r, int32_t pad_b, int32_t fill,
                          int32_t m11, int32_t dtype, dd_stream_t stream);
 
+/* Image input, the other direction: uint8 camera frames -> the normalised pixel values the VAE encoder takes, i.e. the
+ * reference's dataset transform  pil.resize((newW, newH)).crop(box) -> ToTensor -> Normalize(mean, std)  in one launch:
+ *   t[r, X, c]   = clamp8( ((1 << 21) + sum_{j < bx[X].count} in[r, bx[X].xmin + j, c] * kx[X][j]) >> 22 )
+ *   p[Y, X, c]   = clamp8( ((1 << 21) + sum_{j < by[Y].count} t[by[Y].xmin + j, X, c] * ky[Y][j]) >> 22 )
+ *   out[.., c]   = T( lut[c][p[Y, X, c]] )                                  one rounding, to `dtype`
+ * — the formulas of dd_image_resample_u8 (int32, arithmetic shift, the horizontal pass first and rounded to a byte), on
+ * bytes that are already there.
+ * in: (m, h, w, 3) bytes, contiguous, device memory, any alignment.
+ * Tables: as for dd_image_resample_u8 (xmin absolute into `in`), but kx / bx hold `ow` rows and ky / by `oh` rows that
+ * START at the first output column / row of the crop: the caller passes the tables of the resized image offset by the
+ * crop's left / top, and ow x oh is the crop's size.  Nothing outside the crop is computed.
+ * lut: float[3][256], device memory: the normalisation per channel, built by the caller (for torchvision's ToTensor +
+ * Normalize: lut[c][b] = (float(b) / 255 - mean[c]) / std[c] in float32).  The kernel does no floating-point arithmetic.
+ * out, in `dtype` (DD_F16, DD_BF16 or DD_F32):
+ *   layout 0: (m, 3, oh, ow) NCHW;
+ *   layout 1: (m * oh * ow, 8) channels-last rows with channels 3..7 written as zero (what conv_in of the VAE encoder
+ *             reads); out 16-byte aligned.
+ * A workgroup's LDS slice is sized from ksize alone (in / out <= max(ksize - 1, 4) / 4 for PIL's tables); entries of other
+ * tables are clamped to the image and to that slice: the result is then unspecified, nothing outside the buffers is
+ * touched.  NULL pointers, non-positive sizes, an unknown dtype or layout, a misaligned layout-1 out: DD_ERR_BAD_ARG.
+ * ksx, ksy > DD_IMAGE_MAX_KSIZE, m > 65535, a side of 2^24 or more, no tile that fits 64 KB of LDS: DD_ERR_UNSUPPORTED.
+ * Both are decided before anything is launched. */
+int dd_image_load_u8(const uint8_t* in, void* out, int32_t m, int32_t h, int32_t w, int32_t oh, int32_t ow,
+                     const int32_t* kx, const int32_t* bx, int32_t ksx, const int32_t* ky, const int32_t* by,
+                     int32_t ksy, const float* lut, int32_t dtype, int32_t layout, dd_stream_t stream);
+
 /* ------------------------------------------------------------------------- *
  * CLIP text encoder (csrc/clip.hip): the SD-v1.5 `text_encoder` (transformers.CLIPTextModel) that the reference calls at
  * runner/base_runner.py:119,511-514, runner/multiview_runner.py:145,427-428 (`text_encoder(ids)[0]`), through diffusers'
