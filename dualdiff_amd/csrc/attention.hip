@@ -541,10 +541,8 @@ extern "C" int dd_attention(const dd_attn_desc* d, dd_stream_t stream) {
   AttnParams p{};
   const int rc = attn_prepare(d, p);
   if (rc != DD_OK) return rc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
-  if (d->dtype == DD_F16) return launch_attn_t<_Float16>(d, p, s);
-  return launch_attn_t<__bf16>(d, p, s);
+  return dd_dispatch16(d->dtype, [&](auto t) { return launch_attn_t<typename decltype(t)::type>(d, p, dd_stream(stream)); });
 }
 
 extern "C" const char* dd_attention_kernel_name(const dd_attn_desc* d) {

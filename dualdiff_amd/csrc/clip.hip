@@ -236,15 +236,13 @@ extern "C" int dd_clip_embed(const int64_t* ids, const void* tok, const void* po
   const int64_t nb_rows = (chunks + 255) / 256;
   const int64_t nb = nb_rows + (batch + 3) / 4;
   if (nb >= ((int64_t)1 << 31)) return DD_ERR_UNSUPPORTED;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL(dd_clip_embed_kernel<_Float16>, dim3((unsigned)nb), dim3(256), 0, s, ids, (const _Float16*)tok,
-                       (const _Float16*)pos, (_Float16*)out, pool_index, batch, l, c, vocab, eos_token_id, (int)nb_rows);
-  else
-    hipLaunchKernelGGL(dd_clip_embed_kernel<__bf16>, dim3((unsigned)nb), dim3(256), 0, s, ids, (const __bf16*)tok,
-                       (const __bf16*)pos, (__bf16*)out, pool_index, batch, l, c, vocab, eos_token_id, (int)nb_rows);
-  return dd_check_launch();
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dd_clip_embed_kernel<T>, dim3((unsigned)nb), dim3(256), 0, dd_stream(stream), ids, (const T*)tok,
+                       (const T*)pos, (T*)out, pool_index, batch, l, c, vocab, eos_token_id, (int)nb_rows);
+    return dd_check_launch();
+  });
 }
 
 extern "C" int dd_causal_attention(const void* q, const void* k, const void* v, void* o, int64_t ldq, int64_t ldk,
@@ -267,11 +265,12 @@ extern "C" int dd_causal_attention(const void* q, const void* k, const void* v, 
   p.qbs = q_batch_stride; p.kbs = k_batch_stride; p.vbs = v_batch_stride; p.obs = o_batch_stride;
   p.l = l; p.heads = heads; p.nqt = nqt;
   p.scale_log2 = scale * 1.44269504088896340736f;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)(batch * heads * nqt));
   dd_clear_error();
   const size_t smem = (size_t)((nqt + 1) / 2) * 32 * CA_VSTR * 2;   // <= 18 KB
-  if (dtype == DD_F16) hipLaunchKernelGGL(dd_causal_attn_kernel<_Float16>, grid, dim3(64), smem, s, p);
-  else hipLaunchKernelGGL(dd_causal_attn_kernel<__bf16>, grid, dim3(64), smem, s, p);
-  return dd_check_launch();
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dd_causal_attn_kernel<T>, grid, dim3(64), smem, dd_stream(stream), p);
+    return dd_check_launch();
+  });
 }

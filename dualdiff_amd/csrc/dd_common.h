@@ -1,4 +1,5 @@
-// Shared device helpers for the gfx950 kernels (wave64, MFMA 16x16x32).
+// Shared device helpers for the gfx950 kernels (wave64, MFMA 16x16x32), and the host-side dtype dispatch of the
+// extern "C" launchers (dd_dispatch16 / dd_dispatch32 at the end): a new entry point writes its launch once, over T.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -127,6 +128,7 @@ static inline void dd_clear_error() { (void)hipGetLastError(); }
 static inline int dd_check_launch() {
   return hipGetLastError() == hipSuccess ? DD_OK : DD_ERR_LAUNCH;
 }
+static inline hipStream_t dd_stream(dd_stream_t stream) { return reinterpret_cast<hipStream_t>(stream); }
 static inline bool dd_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // Kernels that need more than 64 KB of dynamic LDS must raise hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -140,4 +142,22 @@ static inline void dd_ensure_dyn_lds(const void* kern, size_t smem, std::atomic<
   if (done.load(std::memory_order_acquire) & bit) return;
   (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   done.fetch_or(bit, std::memory_order_release);
+}
+
+// Element-type dispatch of the launchers: f is a generic lambda that names its type with
+//   [&](auto t) { using T = typename decltype(t)::type; ...launch kernel<T>...; return dd_check_launch(); }
+// so that a launch's argument list is written once.  The fall-through is a backstop: every entry point still
+// validates its dtype itself, in the order its return codes promise, before the first HIP runtime call.
+template <typename T> struct dd_tag { using type = T; };
+template <typename F>
+static inline int dd_dispatch16(int32_t dtype, F&& f) {
+  if (dtype == DD_F16) return f(dd_tag<_Float16>{});
+  if (dtype == DD_BF16) return f(dd_tag<__bf16>{});
+  return DD_ERR_BAD_ARG;
+}
+// ... and float for DD_F32 (image.hip, the Fourier launchers, dd_box_tokens' points); a type pair is two nested calls
+template <typename F>
+static inline int dd_dispatch32(int32_t dtype, F&& f) {
+  if (dtype == DD_F32) return f(dd_tag<float>{});
+  return dd_dispatch16(dtype, f);
 }

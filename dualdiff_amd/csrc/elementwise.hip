@@ -468,80 +468,66 @@ extern "C" int dd_add(const void* a, const void* b, const void* c, void* y, int6
   if (!a || !b || !y || n <= 0 || (n & 7)) return DD_ERR_BAD_ARG;
   if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
   if (!dd_aligned16(a) || !dd_aligned16(b) || !dd_aligned16(y) || (c && !dd_aligned16(c))) return DD_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
   const int64_t nvec = n / 8;
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL(dd_add_kernel<_Float16>, dim3(grid_for(nvec)), dim3(256), 0, s,
-                       (const _Float16*)a, (const _Float16*)b, (const _Float16*)c, (_Float16*)y, nvec);
-  else
-    hipLaunchKernelGGL(dd_add_kernel<__bf16>, dim3(grid_for(nvec)), dim3(256), 0, s,
-                       (const __bf16*)a, (const __bf16*)b, (const __bf16*)c, (__bf16*)y, nvec);
-  return dd_check_launch();
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dd_add_kernel<T>, dim3(grid_for(nvec)), dim3(256), 0, dd_stream(stream),
+                       (const T*)a, (const T*)b, (const T*)c, (T*)y, nvec);
+    return dd_check_launch();
+  });
+}
+
+// dd_scale (OP 0, y = sc * x) and dd_silu (OP 1, the scalar is unused)
+template <int OP>
+static int launch_unary(const void* x, void* y, float sc, int64_t n, int32_t dtype, dd_stream_t stream) {
+  if (!x || !y || n <= 0 || (n & 7)) return DD_ERR_BAD_ARG;
+  if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
+  if (!dd_aligned16(x) || !dd_aligned16(y)) return DD_ERR_BAD_ARG;
+  dd_clear_error();
+  const int64_t nvec = n / 8;
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((dd_unary_kernel<T, OP>), dim3(grid_for(nvec)), dim3(256), 0, dd_stream(stream),
+                       (const T*)x, (T*)y, sc, nvec);
+    return dd_check_launch();
+  });
 }
 
 extern "C" int dd_scale(const void* x, void* y, float sc, int64_t n, int32_t dtype, dd_stream_t stream) {
-  if (!x || !y || n <= 0 || (n & 7)) return DD_ERR_BAD_ARG;
-  if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
-  if (!dd_aligned16(x) || !dd_aligned16(y)) return DD_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  dd_clear_error();
-  const int64_t nvec = n / 8;
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL((dd_unary_kernel<_Float16, 0>), dim3(grid_for(nvec)), dim3(256), 0, s,
-                       (const _Float16*)x, (_Float16*)y, sc, nvec);
-  else
-    hipLaunchKernelGGL((dd_unary_kernel<__bf16, 0>), dim3(grid_for(nvec)), dim3(256), 0, s,
-                       (const __bf16*)x, (__bf16*)y, sc, nvec);
-  return dd_check_launch();
+  return launch_unary<0>(x, y, sc, n, dtype, stream);
 }
 
 extern "C" int dd_silu(const void* x, void* y, int64_t n, int32_t dtype, dd_stream_t stream) {
-  if (!x || !y || n <= 0 || (n & 7)) return DD_ERR_BAD_ARG;
-  if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
-  if (!dd_aligned16(x) || !dd_aligned16(y)) return DD_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  dd_clear_error();
-  const int64_t nvec = n / 8;
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL((dd_unary_kernel<_Float16, 1>), dim3(grid_for(nvec)), dim3(256), 0, s,
-                       (const _Float16*)x, (_Float16*)y, 1.f, nvec);
-  else
-    hipLaunchKernelGGL((dd_unary_kernel<__bf16, 1>), dim3(grid_for(nvec)), dim3(256), 0, s,
-                       (const __bf16*)x, (__bf16*)y, 1.f, nvec);
-  return dd_check_launch();
+  return launch_unary<1>(x, y, 1.f, n, dtype, stream);
 }
 
 extern "C" int dd_nchw_to_nhwc(const void* x, void* y, int32_t m, int32_t c, int32_t hw,
                                int32_t c_pad, int32_t dtype, dd_stream_t stream) {
   if (!x || !y || m <= 0 || c <= 0 || hw <= 0 || c_pad < c) return DD_ERR_BAD_ARG;
   if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
   const int64_t total = (int64_t)m * hw * c_pad;
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL(dd_nchw_to_nhwc_kernel<_Float16>, dim3(grid_for(total)), dim3(256), 0, s,
-                       (const _Float16*)x, (_Float16*)y, m, c, hw, c_pad);
-  else
-    hipLaunchKernelGGL(dd_nchw_to_nhwc_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, s,
-                       (const __bf16*)x, (__bf16*)y, m, c, hw, c_pad);
-  return dd_check_launch();
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dd_nchw_to_nhwc_kernel<T>, dim3(grid_for(total)), dim3(256), 0, dd_stream(stream),
+                       (const T*)x, (T*)y, m, c, hw, c_pad);
+    return dd_check_launch();
+  });
 }
 
 extern "C" int dd_nhwc_to_nchw(const void* x, void* y, int32_t m, int32_t c, int32_t hw,
                                int32_t ldx, int32_t dtype, dd_stream_t stream) {
   if (!x || !y || m <= 0 || c <= 0 || hw <= 0 || ldx < c) return DD_ERR_BAD_ARG;
   if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
   const int64_t total = (int64_t)m * hw * c;
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL(dd_nhwc_to_nchw_kernel<_Float16>, dim3(grid_for(total)), dim3(256), 0, s,
-                       (const _Float16*)x, (_Float16*)y, m, c, hw, ldx);
-  else
-    hipLaunchKernelGGL(dd_nhwc_to_nchw_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, s,
-                       (const __bf16*)x, (__bf16*)y, m, c, hw, ldx);
-  return dd_check_launch();
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dd_nhwc_to_nchw_kernel<T>, dim3(grid_for(total)), dim3(256), 0, dd_stream(stream),
+                       (const T*)x, (T*)y, m, c, hw, ldx);
+    return dd_check_launch();
+  });
 }
 
 extern "C" int dd_timestep_embedding(const float* t, void* out, int32_t n, int32_t dim,
@@ -549,16 +535,14 @@ extern "C" int dd_timestep_embedding(const float* t, void* out, int32_t n, int32
                                      int32_t dtype, dd_stream_t stream) {
   if (!t || !out || n <= 0 || dim <= 0 || (dim & 1)) return DD_ERR_BAD_ARG;
   if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
   const int total = n * (dim / 2);
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL(dd_timestep_embedding_kernel<_Float16>, dim3(grid_for(total)), dim3(256), 0, s,
-                       t, (_Float16*)out, n, dim, flip_sin_to_cos, freq_shift);
-  else
-    hipLaunchKernelGGL(dd_timestep_embedding_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, s,
-                       t, (__bf16*)out, n, dim, flip_sin_to_cos, freq_shift);
-  return dd_check_launch();
+  return dd_dispatch16(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(dd_timestep_embedding_kernel<T>, dim3(grid_for(total)), dim3(256), 0, dd_stream(stream),
+                       t, (T*)out, n, dim, flip_sin_to_cos, freq_shift);
+    return dd_check_launch();
+  });
 }
 
 extern "C" int dd_ors_project(const uint8_t* occ, const float* origin, const float* dir, uint8_t* labels,
@@ -566,44 +550,29 @@ extern "C" int dd_ors_project(const uint8_t* occ, const float* origin, const flo
                               int32_t keep_fg, int32_t keep_bg, int32_t dtype, dd_stream_t stream) {
   if (!occ || !origin || !dir || (!labels && !cond) || n_cam <= 0 || hw <= 0 || samples <= 0) return DD_ERR_BAD_ARG;
   if (cond && dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
   const int64_t total = (int64_t)n_cam * samples * hw;
   const unsigned g = (unsigned)grid_for(total > (1 << 30) ? (1 << 30) : (int)total);
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL(dd_ors_project_kernel<_Float16>, dim3(g), dim3(256), 0, s, occ, origin, dir, labels,
-                       (_Float16*)cond, n_cam, hw, samples, step, keep_fg, keep_bg);
-  else
-    hipLaunchKernelGGL(dd_ors_project_kernel<__bf16>, dim3(g), dim3(256), 0, s, occ, origin, dir, labels,
-                       (__bf16*)cond, n_cam, hw, samples, step, keep_fg, keep_bg);
-  return dd_check_launch();
+  // labels only: no T is written and the dtype is not validated; any code but DD_F16 runs the bf16 instantiation
+  return dd_dispatch16(!cond && dtype != DD_F16 ? DD_BF16 : dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dd_ors_project_kernel<T>, dim3(g), dim3(256), 0, dd_stream(stream), occ, origin, dir, labels,
+                       (T*)cond, n_cam, hw, samples, step, keep_fg, keep_bg);
+    return dd_check_launch();
+  });
 }
 
 extern "C" int dd_softmax_rows(const float* s, void* p, int64_t rows, int32_t cols, int64_t lds, int64_t ldp,
                                int32_t dtype, dd_stream_t stream) {
   if (!s || !p || rows <= 0 || cols <= 0 || lds < cols || ldp < cols) return DD_ERR_BAD_ARG;
   if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
   const unsigned g = (unsigned)((rows + 3) / 4);
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL(dd_softmax_rows_kernel<_Float16>, dim3(g), dim3(256), 0, st, s, (_Float16*)p, rows, cols, lds, ldp);
-  else
-    hipLaunchKernelGGL(dd_softmax_rows_kernel<__bf16>, dim3(g), dim3(256), 0, st, s, (__bf16*)p, rows, cols, lds, ldp);
-  return dd_check_launch();
-}
-
-template <typename TI>
-int launch_fourier(const void* x, void* out, int64_t total, int dims, const FourierFreqs& fr, int nf, int inc,
-                   int out_dtype, hipStream_t s) {
-  const unsigned g = (unsigned)grid_for(total > (1 << 30) ? (1 << 30) : (int)total);
-  if (out_dtype == DD_F16)
-    hipLaunchKernelGGL((dd_fourier_embed_kernel<TI, _Float16>), dim3(g), dim3(256), 0, s, (const TI*)x, (_Float16*)out, total, dims, fr, nf, inc);
-  else if (out_dtype == DD_BF16)
-    hipLaunchKernelGGL((dd_fourier_embed_kernel<TI, __bf16>), dim3(g), dim3(256), 0, s, (const TI*)x, (__bf16*)out, total, dims, fr, nf, inc);
-  else
-    hipLaunchKernelGGL((dd_fourier_embed_kernel<TI, float>), dim3(g), dim3(256), 0, s, (const TI*)x, (float*)out, total, dims, fr, nf, inc);
-  return dd_check_launch();
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dd_softmax_rows_kernel<T>, dim3(g), dim3(256), 0, dd_stream(stream), s, (T*)p, rows, cols, lds, ldp);
+    return dd_check_launch();
+  });
 }
 
 extern "C" int dd_fourier_embed(const void* x, void* out, int64_t rows, int32_t dims, const float* freqs,
@@ -614,13 +583,19 @@ extern "C" int dd_fourier_embed(const void* x, void* out, int64_t rows, int32_t 
   if (in_dtype < 0 || in_dtype > DD_F32 || out_dtype < 0 || out_dtype > DD_F32) return DD_ERR_BAD_ARG;
   FourierFreqs fr{};
   for (int i = 0; i < num_freqs; ++i) fr.f[i] = freqs[i];
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
   const int64_t total = rows * dims;
   const int inc = include_input ? 1 : 0;
-  if (in_dtype == DD_F16) return launch_fourier<_Float16>(x, out, total, dims, fr, num_freqs, inc, out_dtype, s);
-  if (in_dtype == DD_BF16) return launch_fourier<__bf16>(x, out, total, dims, fr, num_freqs, inc, out_dtype, s);
-  return launch_fourier<float>(x, out, total, dims, fr, num_freqs, inc, out_dtype, s);
+  const unsigned g = (unsigned)grid_for(total > (1 << 30) ? (1 << 30) : (int)total);
+  return dd_dispatch32(in_dtype, [&](auto ti) {
+    return dd_dispatch32(out_dtype, [&](auto to) {
+      using TI = typename decltype(ti)::type;
+      using TO = typename decltype(to)::type;
+      hipLaunchKernelGGL((dd_fourier_embed_kernel<TI, TO>), dim3(g), dim3(256), 0, dd_stream(stream), (const TI*)x,
+                         (TO*)out, total, dims, fr, num_freqs, inc);
+      return dd_check_launch();
+    });
+  });
 }
 
 extern "C" int dd_conv3x3_small_cout(const void* x, const void* w, const void* bias, void* y_nchw,
@@ -630,19 +605,15 @@ extern "C" int dd_conv3x3_small_cout(const void* x, const void* w, const void* b
   if ((cin & 7) || cout > 8) return DD_ERR_UNSUPPORTED;
   if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
   if (!dd_aligned16(x) || !dd_aligned16(w)) return DD_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
   const int64_t npix = (int64_t)m * h * wd;
   const unsigned blocks = (unsigned)((npix + 3) / 4);
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL((dd_conv3x3_small_kernel<_Float16, 8>), dim3(blocks), dim3(256), 0, s,
-                       (const _Float16*)x, (const _Float16*)w, (const _Float16*)bias,
-                       (_Float16*)y_nchw, m, h, wd, cin, cout);
-  else
-    hipLaunchKernelGGL((dd_conv3x3_small_kernel<__bf16, 8>), dim3(blocks), dim3(256), 0, s,
-                       (const __bf16*)x, (const __bf16*)w, (const __bf16*)bias,
-                       (__bf16*)y_nchw, m, h, wd, cin, cout);
-  return dd_check_launch();
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((dd_conv3x3_small_kernel<T, 8>), dim3(blocks), dim3(256), 0, dd_stream(stream),
+                       (const T*)x, (const T*)w, (const T*)bias, (T*)y_nchw, m, h, wd, cin, cout);
+    return dd_check_launch();
+  });
 }
 
 template <typename T, int CIN, int COUT, int STRIDE>
@@ -678,10 +649,11 @@ extern "C" int dd_conv3x3_thin(const void* x, const void* w, const void* bias, v
   if (stride != 1 && stride != 2) return DD_ERR_UNSUPPORTED;
   if (m > 65535) return DD_ERR_UNSUPPORTED;
   const int hout = (hin - 1) / stride + 1, wout = (win - 1) / stride + 1;      // kernel 3, pad 1
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
-  if (dtype == DD_F16) return launch_thin_t<_Float16>(x, w, bias, y, m, hin, win, hout, wout, cin, cout, stride, silu, s);
-  return launch_thin_t<__bf16>(x, w, bias, y, m, hin, win, hout, wout, cin, cout, stride, silu, s);
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_thin_t<T>(x, w, bias, y, m, hin, win, hout, wout, cin, cout, stride, silu, dd_stream(stream));
+  });
 }
 
 extern "C" int dd_cfg_ddim_step(const void* eps, const void* x, void* x_out, void* x_dup,
@@ -689,17 +661,13 @@ extern "C" int dd_cfg_ddim_step(const void* eps, const void* x, void* x_out, voi
                                 int32_t dtype, dd_stream_t stream) {
   if (!eps || !x || !x_out || !coef || n <= 0) return DD_ERR_BAD_ARG;
   if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL(dd_cfg_ddim_kernel<_Float16>, dim3(grid_for(n)), dim3(256), 0, s,
-                       (const _Float16*)eps, (const _Float16*)x, (_Float16*)x_out, (_Float16*)x_dup,
-                       coef, guidance, n);
-  else
-    hipLaunchKernelGGL(dd_cfg_ddim_kernel<__bf16>, dim3(grid_for(n)), dim3(256), 0, s,
-                       (const __bf16*)eps, (const __bf16*)x, (__bf16*)x_out, (__bf16*)x_dup,
-                       coef, guidance, n);
-  return dd_check_launch();
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dd_cfg_ddim_kernel<T>, dim3(grid_for(n)), dim3(256), 0, dd_stream(stream),
+                       (const T*)eps, (const T*)x, (T*)x_out, (T*)x_dup, coef, guidance, n);
+    return dd_check_launch();
+  });
 }
 
 extern "C" int dd_cfg_unipc_step(const void* eps, const void* x, void* x_out, void* x_dup, float* last,
@@ -707,17 +675,13 @@ extern "C" int dd_cfg_unipc_step(const void* eps, const void* x, void* x_out, vo
                                  int32_t dtype, dd_stream_t stream) {
   if (!eps || !x || !x_out || !last || !m1 || !m2 || !coef || n <= 0) return DD_ERR_BAD_ARG;
   if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL(dd_cfg_unipc_kernel<_Float16>, dim3(grid_for(n)), dim3(256), 0, s,
-                       (const _Float16*)eps, (const _Float16*)x, (_Float16*)x_out, (_Float16*)x_dup,
-                       last, m1, m2, coef, guidance, n);
-  else
-    hipLaunchKernelGGL(dd_cfg_unipc_kernel<__bf16>, dim3(grid_for(n)), dim3(256), 0, s,
-                       (const __bf16*)eps, (const __bf16*)x, (__bf16*)x_out, (__bf16*)x_dup,
-                       last, m1, m2, coef, guidance, n);
-  return dd_check_launch();
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dd_cfg_unipc_kernel<T>, dim3(grid_for(n)), dim3(256), 0, dd_stream(stream),
+                       (const T*)eps, (const T*)x, (T*)x_out, (T*)x_dup, last, m1, m2, coef, guidance, n);
+    return dd_check_launch();
+  });
 }
 
 // Given-view launches: grid (x-blocks per view, view-instances); validation happens before any HIP call.
@@ -730,17 +694,28 @@ static int given_geometry(int64_t n, int64_t view_elems, dim3* grid) {
   return DD_OK;
 }
 
-template <typename T, typename K>
-static void launch_given(dim3 grid, hipStream_t s, int32_t mode, const void* eps, const void* x, void* x_out,
-                         void* x_dup, float* last, float* m1, float* m2, const float* coef, float guidance,
-                         const uint8_t* given, const float* clean, const void* noise0, const float* gcoef, int64_t n,
-                         int view_elems) {
-  if (mode == 1)
-    hipLaunchKernelGGL((dd_cfg_given_kernel<T, 1, K>), grid, dim3(256), 0, s, (const T*)eps, (const T*)x, (T*)x_out,
-                       (T*)x_dup, last, m1, m2, coef, guidance, given, clean, (const T*)noise0, gcoef, n, view_elems);
-  else
-    hipLaunchKernelGGL((dd_cfg_given_kernel<T, 2, K>), grid, dim3(256), 0, s, (const T*)eps, (const T*)x, (T*)x_out,
-                       (T*)x_dup, last, m1, m2, coef, guidance, given, clean, (const T*)noise0, gcoef, n, view_elems);
+// both given-view steps: K is the solver's coefficient block; DDIM passes null last / m1 / m2
+template <typename K>
+static int launch_given(int32_t mode, const void* eps, const void* x, void* x_out, void* x_dup, float* last, float* m1,
+                        float* m2, const float* coef, float guidance, const uint8_t* given, const float* clean,
+                        const void* noise0, const float* gcoef, int64_t n, int64_t view_elems, int32_t dtype,
+                        dd_stream_t stream) {
+  if (mode != 1 && mode != 2) return DD_ERR_BAD_ARG;
+  if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
+  dim3 grid;
+  const int rc = given_geometry(n, view_elems, &grid);
+  if (rc != DD_OK) return rc;
+  dd_clear_error();
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    auto go = [&](auto kern) {
+      hipLaunchKernelGGL(kern, grid, dim3(256), 0, dd_stream(stream), (const T*)eps, (const T*)x, (T*)x_out, (T*)x_dup,
+                         last, m1, m2, coef, guidance, given, clean, (const T*)noise0, gcoef, n, (int)view_elems);
+    };
+    if (mode == 1) go(dd_cfg_given_kernel<T, 1, K>);
+    else go(dd_cfg_given_kernel<T, 2, K>);
+    return dd_check_launch();
+  });
 }
 
 extern "C" int dd_cfg_ddim_step_given(const void* eps, const void* x, void* x_out, void* x_dup, const float* coef,
@@ -748,20 +723,8 @@ extern "C" int dd_cfg_ddim_step_given(const void* eps, const void* x, void* x_ou
                                       const float* gcoef, int32_t mode, int64_t n, int64_t view_elems, int32_t dtype,
                                       dd_stream_t stream) {
   if (!eps || !x || !x_out || !coef || !given || !clean || !noise0 || !gcoef) return DD_ERR_BAD_ARG;
-  if (mode != 1 && mode != 2) return DD_ERR_BAD_ARG;
-  if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
-  dim3 grid;
-  const int rc = given_geometry(n, view_elems, &grid);
-  if (rc != DD_OK) return rc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  dd_clear_error();
-  if (dtype == DD_F16)
-    launch_given<_Float16, dd_ddim_coef>(grid, s, mode, eps, x, x_out, x_dup, nullptr, nullptr, nullptr, coef, guidance,
-                                         given, clean, noise0, gcoef, n, (int)view_elems);
-  else
-    launch_given<__bf16, dd_ddim_coef>(grid, s, mode, eps, x, x_out, x_dup, nullptr, nullptr, nullptr, coef, guidance,
-                                       given, clean, noise0, gcoef, n, (int)view_elems);
-  return dd_check_launch();
+  return launch_given<dd_ddim_coef>(mode, eps, x, x_out, x_dup, nullptr, nullptr, nullptr, coef, guidance, given, clean,
+                                    noise0, gcoef, n, view_elems, dtype, stream);
 }
 
 extern "C" int dd_cfg_unipc_step_given(const void* eps, const void* x, void* x_out, void* x_dup, float* last, float* m1,
@@ -770,20 +733,8 @@ extern "C" int dd_cfg_unipc_step_given(const void* eps, const void* x, void* x_o
                                        int64_t n, int64_t view_elems, int32_t dtype, dd_stream_t stream) {
   if (!eps || !x || !x_out || !last || !m1 || !m2 || !coef || !given || !clean || !noise0 || !gcoef)
     return DD_ERR_BAD_ARG;
-  if (mode != 1 && mode != 2) return DD_ERR_BAD_ARG;
-  if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
-  dim3 grid;
-  const int rc = given_geometry(n, view_elems, &grid);
-  if (rc != DD_OK) return rc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  dd_clear_error();
-  if (dtype == DD_F16)
-    launch_given<_Float16, dd_unipc_coef>(grid, s, mode, eps, x, x_out, x_dup, last, m1, m2, coef, guidance, given,
-                                          clean, noise0, gcoef, n, (int)view_elems);
-  else
-    launch_given<__bf16, dd_unipc_coef>(grid, s, mode, eps, x, x_out, x_dup, last, m1, m2, coef, guidance, given,
-                                        clean, noise0, gcoef, n, (int)view_elems);
-  return dd_check_launch();
+  return launch_given<dd_unipc_coef>(mode, eps, x, x_out, x_dup, last, m1, m2, coef, guidance, given, clean, noise0,
+                                     gcoef, n, view_elems, dtype, stream);
 }
 
 extern "C" int dd_given_views_noise(void* x, void* x_dup, const uint8_t* given, const float* clean, const void* noise0,
@@ -794,15 +745,13 @@ extern "C" int dd_given_views_noise(void* x, void* x_dup, const uint8_t* given, 
   dim3 grid;
   const int rc = given_geometry(n, view_elems, &grid);
   if (rc != DD_OK) return rc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL(dd_given_noise_kernel<_Float16>, grid, dim3(256), 0, s, (_Float16*)x, (_Float16*)x_dup, given,
-                       clean, (const _Float16*)noise0, sqrt_acp, sqrt_1m_acp, (int)view_elems);
-  else
-    hipLaunchKernelGGL(dd_given_noise_kernel<__bf16>, grid, dim3(256), 0, s, (__bf16*)x, (__bf16*)x_dup, given,
-                       clean, (const __bf16*)noise0, sqrt_acp, sqrt_1m_acp, (int)view_elems);
-  return dd_check_launch();
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dd_given_noise_kernel<T>, grid, dim3(256), 0, dd_stream(stream), (T*)x, (T*)x_dup, given,
+                       clean, (const T*)noise0, sqrt_acp, sqrt_1m_acp, (int)view_elems);
+    return dd_check_launch();
+  });
 }
 
 // Timing probe (bench.py's KernelTimer calibration): ONE wave that waits `ticks` ticks of the constant 100 MHz
@@ -823,7 +772,7 @@ __global__ __launch_bounds__(64) void dd_probe_spin_kernel(uint64_t* stamps, uin
 extern "C" int dd_probe_spin(uint64_t* stamps, uint32_t ticks_100mhz, dd_stream_t stream) {
   if (!stamps || ticks_100mhz == 0 || ticks_100mhz > 100000000u) return DD_ERR_BAD_ARG;
   dd_clear_error();
-  hipLaunchKernelGGL(dd_probe_spin_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), stamps, ticks_100mhz);
+  hipLaunchKernelGGL(dd_probe_spin_kernel, dim3(1), dim3(64), 0, dd_stream(stream), stamps, ticks_100mhz);
   return dd_check_launch();
 }
 

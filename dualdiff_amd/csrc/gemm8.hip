@@ -310,10 +310,11 @@ extern "C" int dd_rowquant_fp8(const void* x, const void* gamma, const void* bet
   if ((gamma == nullptr) != (beta == nullptr)) return DD_ERR_BAD_ARG;
   if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
   if (!dd_aligned16(x) || !dd_aligned16(q) || (gamma && (!dd_aligned16(gamma) || !dd_aligned16(beta)))) return DD_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
-  if (dtype == DD_F16) return launch_rowquant<_Float16>(x, gamma, beta, reinterpret_cast<uint8_t*>(q), scale, rows, c, ldq, eps, s);
-  return launch_rowquant<__bf16>(x, gamma, beta, reinterpret_cast<uint8_t*>(q), scale, rows, c, ldq, eps, s);
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_rowquant<T>(x, gamma, beta, reinterpret_cast<uint8_t*>(q), scale, rows, c, ldq, eps, dd_stream(stream));
+  });
 }
 
 extern "C" int dd_gemm8(const dd_gemm8_desc* d, dd_stream_t stream) {
@@ -337,8 +338,6 @@ extern "C" int dd_gemm8(const dd_gemm8_desc* d, dd_stream_t stream) {
   const int bn_out = p.geglu ? G8_BN / 2 : G8_BN;
   p.tiles_m = (d->rows + G8_BM - 1) / G8_BM; p.tiles_n = (d->n + bn_out - 1) / bn_out;
   p.hm_d = d->out_headmajor_d; p.hm_planes = d->hm_scaled_planes; p.hm_scale = d->hm_scale;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
-  if (d->dtype == DD_F16) return launch_gemm8<_Float16>(p, s);
-  return launch_gemm8<__bf16>(p, s);
+  return dd_dispatch16(d->dtype, [&](auto t) { return launch_gemm8<typename decltype(t)::type>(p, dd_stream(stream)); });
 }

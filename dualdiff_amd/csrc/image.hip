@@ -384,14 +384,6 @@ void dd_image_load_kernel(const LoadArgs a) {
   }
 }
 
-template <typename T>
-static inline void launch_load(const LoadArgs& a, int layout, dim3 grid, size_t lds, hipStream_t s) {
-  if (layout == 0)
-    hipLaunchKernelGGL((dd_image_load_kernel<T, 0>), grid, dim3(kThreads), lds, s, a);
-  else
-    hipLaunchKernelGGL((dd_image_load_kernel<T, 1>), grid, dim3(kThreads), lds, s, a);
-}
-
 }  // namespace
 
 extern "C" int dd_image_quantize_u8(const void* x, uint8_t* out, int32_t m, int32_t h, int32_t w, int32_t m11,
@@ -400,16 +392,14 @@ extern "C" int dd_image_quantize_u8(const void* x, uint8_t* out, int32_t m, int3
   if (dtype != DD_F16 && dtype != DD_BF16 && dtype != DD_F32) return DD_ERR_BAD_ARG;
   const int64_t hw = (int64_t)h * w;
   if (m > 65535 || hw >= ((int64_t)1 << 31)) return DD_ERR_UNSUPPORTED;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)((hw + 4 * kThreads - 1) / (4 * kThreads)), (unsigned)m);
   dd_clear_error();
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL(dd_image_quantize_kernel<_Float16>, grid, dim3(kThreads), 0, s, (const _Float16*)x, out, (int32_t)hw, m11);
-  else if (dtype == DD_BF16)
-    hipLaunchKernelGGL(dd_image_quantize_kernel<__bf16>, grid, dim3(kThreads), 0, s, (const __bf16*)x, out, (int32_t)hw, m11);
-  else
-    hipLaunchKernelGGL(dd_image_quantize_kernel<float>, grid, dim3(kThreads), 0, s, (const float*)x, out, (int32_t)hw, m11);
-  return dd_check_launch();
+  return dd_dispatch32(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dd_image_quantize_kernel<T>, grid, dim3(kThreads), 0, dd_stream(stream), (const T*)x, out,
+                       (int32_t)hw, m11);
+    return dd_check_launch();
+  });
 }
 
 extern "C" int dd_image_resample_u8(const void* x, uint8_t* out, int32_t m, int32_t h, int32_t w, int32_t oh, int32_t ow,
@@ -439,16 +429,13 @@ extern "C" int dd_image_resample_u8(const void* x, uint8_t* out, int32_t m, int3
   if (!found) return DD_ERR_UNSUPPORTED;
   const int64_t gx = (wt + a.tw - 1) / a.tw, gy = (ht + a.th - 1) / a.th;
   if (gy > 65535) return DD_ERR_UNSUPPORTED;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)m);
   dd_clear_error();
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL(dd_image_resample_kernel<_Float16>, grid, dim3(kThreads), lds, s, a);
-  else if (dtype == DD_BF16)
-    hipLaunchKernelGGL(dd_image_resample_kernel<__bf16>, grid, dim3(kThreads), lds, s, a);
-  else
-    hipLaunchKernelGGL(dd_image_resample_kernel<float>, grid, dim3(kThreads), lds, s, a);
-  return dd_check_launch();
+  return dd_dispatch32(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dd_image_resample_kernel<T>, grid, dim3(kThreads), lds, dd_stream(stream), a);
+    return dd_check_launch();
+  });
 }
 
 extern "C" int dd_image_load_u8(const uint8_t* in, void* out, int32_t m, int32_t h, int32_t w, int32_t oh, int32_t ow,
@@ -476,14 +463,13 @@ extern "C" int dd_image_load_u8(const uint8_t* in, void* out, int32_t m, int32_t
   if (!found) return DD_ERR_UNSUPPORTED;
   const int64_t gx = ((int64_t)ow + a.tw - 1) / a.tw, gy = ((int64_t)oh + a.th - 1) / a.th;
   if (gy > 65535) return DD_ERR_UNSUPPORTED;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)m);
   dd_clear_error();
-  if (dtype == DD_F16)
-    launch_load<_Float16>(a, layout, grid, lds, s);
-  else if (dtype == DD_BF16)
-    launch_load<__bf16>(a, layout, grid, lds, s);
-  else
-    launch_load<float>(a, layout, grid, lds, s);
-  return dd_check_launch();
+  return dd_dispatch32(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(kThreads), lds, dd_stream(stream), a); };
+    if (layout == 0) go(dd_image_load_kernel<T, 0>);
+    else go(dd_image_load_kernel<T, 1>);
+    return dd_check_launch();
+  });
 }

@@ -567,6 +567,22 @@ int gn_plan(int hw, int c, int* pix_per_split) {
   return (hw + pps - 1) / pps;
 }
 
+// The single-launch GroupNorm of both entry points (SK: the input is dd_groupnorm_splitk's producer sums), in the
+// block size that gn_fused_plan chose.
+template <bool SK>
+int launch_gn_fused(const GnParams& p, int cpb, int vpp, int plc, int nv, int kred, int threads, int32_t dtype,
+                    hipStream_t s) {
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    auto go = [&](auto kern, int th) {
+      hipLaunchKernelGGL(kern, dim3(p.c / cpb, p.m), dim3(th), 0, s, p, cpb, vpp, plc, nv, kred);
+    };
+    if (threads == 256) go(dd_gn_fused_kernel<T, 256, GNF_NV_SMALL, SK>, 256);
+    else go(dd_gn_fused_kernel<T, 1024, GNF_NV_BIG, SK>, 1024);
+    return dd_check_launch();
+  });
+}
+
 }  // namespace
 
 extern "C" int64_t dd_groupnorm_workspace_bytes(int32_t m, int32_t groups) {
@@ -595,29 +611,18 @@ extern "C" int dd_groupnorm_nhwc(const void* x1, int32_t c1, const void* x2, int
   p.m = m; p.hw = hw; p.groups = groups; p.cpg = c / groups; p.eps = eps; p.silu = apply_silu;
   p.ws = reinterpret_cast<float*>(ws) + 64;          // the first 256 B stay reserved; the partial sums follow
   p.nsplit = gn_plan(hw, c, &p.pix_per_split);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t s = dd_stream(stream);
   dd_clear_error();
   int cpb, vpp, plc, nv, kred, threads;
-  if (gn_fused_plan(hw, c, groups, &cpb, &vpp, &plc, &nv, &kred, &threads)) {
-    dim3 fgrid(c / cpb, m);
-    if (threads == 256) {
-      if (dtype == DD_F16) hipLaunchKernelGGL((dd_gn_fused_kernel<_Float16, 256, GNF_NV_SMALL>), fgrid, dim3(256), 0, s, p, cpb, vpp, plc, nv, kred);
-      else hipLaunchKernelGGL((dd_gn_fused_kernel<__bf16, 256, GNF_NV_SMALL>), fgrid, dim3(256), 0, s, p, cpb, vpp, plc, nv, kred);
-    } else {
-      if (dtype == DD_F16) hipLaunchKernelGGL((dd_gn_fused_kernel<_Float16, 1024, GNF_NV_BIG>), fgrid, dim3(1024), 0, s, p, cpb, vpp, plc, nv, kred);
-      else hipLaunchKernelGGL((dd_gn_fused_kernel<__bf16, 1024, GNF_NV_BIG>), fgrid, dim3(1024), 0, s, p, cpb, vpp, plc, nv, kred);
-    }
+  if (gn_fused_plan(hw, c, groups, &cpb, &vpp, &plc, &nv, &kred, &threads))
+    return launch_gn_fused<false>(p, cpb, vpp, plc, nv, kred, threads, dtype, s);
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    const dim3 grid(p.nsplit, m);
+    hipLaunchKernelGGL(dd_gn_stats_kernel<T>, grid, dim3(GN_THREADS), 0, s, p);
+    hipLaunchKernelGGL(dd_gn_apply_kernel<T>, grid, dim3(GN_THREADS), 0, s, p);
     return dd_check_launch();
-  }
-  dim3 grid(p.nsplit, m);
-  if (dtype == DD_F16) {
-    hipLaunchKernelGGL(dd_gn_stats_kernel<_Float16>, grid, dim3(GN_THREADS), 0, s, p);
-    hipLaunchKernelGGL(dd_gn_apply_kernel<_Float16>, grid, dim3(GN_THREADS), 0, s, p);
-  } else {
-    hipLaunchKernelGGL(dd_gn_stats_kernel<__bf16>, grid, dim3(GN_THREADS), 0, s, p);
-    hipLaunchKernelGGL(dd_gn_apply_kernel<__bf16>, grid, dim3(GN_THREADS), 0, s, p);
-  }
-  return dd_check_launch();
+  });
 }
 
 extern "C" int dd_groupnorm_splitk(const float* partial, int32_t nsplit, const void* bias, const void* rowvec,
@@ -639,17 +644,8 @@ extern "C" int dd_groupnorm_splitk(const float* partial, int32_t nsplit, const v
   p.m = m; p.hw = hw; p.groups = groups; p.cpg = c / groups; p.eps = eps; p.silu = apply_silu;
   p.sk_part = partial; p.sk_nsplit = nsplit; p.sk_rows = (int64_t)m * hw;
   p.sk_bias = bias; p.sk_rowvec = rowvec; p.sk_ld_rowvec = ld_rowvec; p.sk_res = res; p.sk_ldres = ldres; p.sk_xout = x_out;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
-  dim3 fgrid(c / cpb, m);
-  if (threads == 256) {
-    if (dtype == DD_F16) hipLaunchKernelGGL((dd_gn_fused_kernel<_Float16, 256, GNF_NV_SMALL, true>), fgrid, dim3(256), 0, s, p, cpb, vpp, plc, nv, kred);
-    else hipLaunchKernelGGL((dd_gn_fused_kernel<__bf16, 256, GNF_NV_SMALL, true>), fgrid, dim3(256), 0, s, p, cpb, vpp, plc, nv, kred);
-  } else {
-    if (dtype == DD_F16) hipLaunchKernelGGL((dd_gn_fused_kernel<_Float16, 1024, GNF_NV_BIG, true>), fgrid, dim3(1024), 0, s, p, cpb, vpp, plc, nv, kred);
-    else hipLaunchKernelGGL((dd_gn_fused_kernel<__bf16, 1024, GNF_NV_BIG, true>), fgrid, dim3(1024), 0, s, p, cpb, vpp, plc, nv, kred);
-  }
-  return dd_check_launch();
+  return launch_gn_fused<true>(p, cpb, vpp, plc, nv, kred, threads, dtype, dd_stream(stream));
 }
 
 extern "C" int dd_groupnorm_is_fused(int32_t hw, int32_t c, int32_t groups) {
@@ -665,20 +661,13 @@ extern "C" int dd_layernorm(const void* x, const void* gamma, const void* beta, 
   if ((c & 7) || c > LN_MAXV * 512) return DD_ERR_UNSUPPORTED;
   if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
   if (!dd_aligned16(x) || !dd_aligned16(y) || !dd_aligned16(gamma) || !dd_aligned16(beta)) return DD_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t s = dd_stream(stream);
   dd_clear_error();
-  if (dtype == DD_F16 ? launch_layernorm_sub<_Float16>(x, gamma, beta, y, rows, c, eps, s)
-                      : launch_layernorm_sub<__bf16>(x, gamma, beta, y, rows, c, eps, s))
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if (!launch_layernorm_sub<T>(x, gamma, beta, y, rows, c, eps, s))
+      hipLaunchKernelGGL(dd_layernorm_kernel<T>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s,
+                         (const T*)x, (const T*)gamma, (const T*)beta, (T*)y, rows, c, eps);
     return dd_check_launch();
-  const unsigned blocks = (unsigned)((rows + 3) / 4);
-  if (dtype == DD_F16) {
-    hipLaunchKernelGGL(dd_layernorm_kernel<_Float16>, dim3(blocks), dim3(256), 0, s,
-                       (const _Float16*)x, (const _Float16*)gamma, (const _Float16*)beta,
-                       (_Float16*)y, rows, c, eps);
-  } else {
-    hipLaunchKernelGGL(dd_layernorm_kernel<__bf16>, dim3(blocks), dim3(256), 0, s,
-                       (const __bf16*)x, (const __bf16*)gamma, (const __bf16*)beta,
-                       (__bf16*)y, rows, c, eps);
-  }
-  return dd_check_launch();
+  });
 }

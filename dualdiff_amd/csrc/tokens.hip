@@ -177,19 +177,6 @@ inline unsigned grid_for(int64_t n, int threads = 256) {
   return (unsigned)(b < 1 ? 1 : (b > 65535 * 4 ? 65535 * 4 : b));
 }
 
-template <typename TI>
-int launch_fourier2(const void* x, void* out, int64_t rows, int dims, const FourierFreqs2& fr, int nf, int inc, int inner,
-                    int64_t so, int64_t si, int64_t sd, int64_t out_ld, int out_dtype, hipStream_t s) {
-  const unsigned g = grid_for(rows * dims);
-  if (out_dtype == DD_F16)
-    hipLaunchKernelGGL((dd_fourier_embed2_kernel<TI, _Float16>), dim3(g), dim3(256), 0, s, (const TI*)x, (_Float16*)out, rows, dims, fr, nf, inc, inner, so, si, sd, out_ld);
-  else if (out_dtype == DD_BF16)
-    hipLaunchKernelGGL((dd_fourier_embed2_kernel<TI, __bf16>), dim3(g), dim3(256), 0, s, (const TI*)x, (__bf16*)out, rows, dims, fr, nf, inc, inner, so, si, sd, out_ld);
-  else
-    hipLaunchKernelGGL((dd_fourier_embed2_kernel<TI, float>), dim3(g), dim3(256), 0, s, (const TI*)x, (float*)out, rows, dims, fr, nf, inc, inner, so, si, sd, out_ld);
-  return dd_check_launch();
-}
-
 template <typename TI, typename T>
 int launch_box(const dd_box_tokens_desc* d, const FourierFreqs2& fr, hipStream_t s) {
   hipLaunchKernelGGL((dd_box_tokens_kernel<TI, T>), dim3(d->rows), dim3(256), 0, s, (const TI*)d->points, d->classes,
@@ -207,19 +194,18 @@ extern "C" int dd_nchw_to_nhwc_views(const void* x, void* y, int32_t m, int32_t 
   if (!x || !y || m <= 0 || c <= 0 || h <= 0 || w <= 0 || views <= 0 || c_pad < c || (c_pad & 7)) return DD_ERR_BAD_ARG;
   if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
   if (!dd_aligned16(y) || (int64_t)m * views > 65535) return DD_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
   const int hw = h * w;
-  if (c_pad <= 8) {
-    const dim3 g((hw + 63) / 64, 1, m * views);
-    if (dtype == DD_F16) hipLaunchKernelGGL((dd_nchw_to_nhwc_tiled_kernel<_Float16, 8>), g, dim3(256), 0, s, (const _Float16*)x, (_Float16*)y, c, h, w, views, c_pad);
-    else hipLaunchKernelGGL((dd_nchw_to_nhwc_tiled_kernel<__bf16, 8>), g, dim3(256), 0, s, (const __bf16*)x, (__bf16*)y, c, h, w, views, c_pad);
-  } else {
-    const dim3 g((hw + 63) / 64, (c_pad + 63) / 64, m * views);
-    if (dtype == DD_F16) hipLaunchKernelGGL((dd_nchw_to_nhwc_tiled_kernel<_Float16, 64>), g, dim3(256), 0, s, (const _Float16*)x, (_Float16*)y, c, h, w, views, c_pad);
-    else hipLaunchKernelGGL((dd_nchw_to_nhwc_tiled_kernel<__bf16, 64>), g, dim3(256), 0, s, (const __bf16*)x, (__bf16*)y, c, h, w, views, c_pad);
-  }
-  return dd_check_launch();
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    auto go = [&](auto kern, unsigned channel_tiles) {
+      hipLaunchKernelGGL(kern, dim3((hw + 63) / 64, channel_tiles, m * views), dim3(256), 0, dd_stream(stream),
+                         (const T*)x, (T*)y, c, h, w, views, c_pad);
+    };
+    if (c_pad <= 8) go(dd_nchw_to_nhwc_tiled_kernel<T, 8>, 1);
+    else go(dd_nchw_to_nhwc_tiled_kernel<T, 64>, (c_pad + 63) / 64);
+    return dd_check_launch();
+  });
 }
 
 extern "C" int dd_fourier_embed_strided(const void* x, void* out, int64_t rows, int32_t dims, const float* freqs,
@@ -234,11 +220,17 @@ extern "C" int dd_fourier_embed_strided(const void* x, void* out, int64_t rows, 
   if (out_ld < inner * width || out_ld - inner * width > dims) return DD_ERR_BAD_ARG;     // at most `dims` pad columns
   FourierFreqs2 fr{};
   for (int i = 0; i < num_freqs; ++i) fr.f[i] = freqs[i];
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
-  if (in_dtype == DD_F16) return launch_fourier2<_Float16>(x, out, rows, dims, fr, num_freqs, inc, inner, stride_outer, stride_inner, stride_dim, out_ld, out_dtype, s);
-  if (in_dtype == DD_BF16) return launch_fourier2<__bf16>(x, out, rows, dims, fr, num_freqs, inc, inner, stride_outer, stride_inner, stride_dim, out_ld, out_dtype, s);
-  return launch_fourier2<float>(x, out, rows, dims, fr, num_freqs, inc, inner, stride_outer, stride_inner, stride_dim, out_ld, out_dtype, s);
+  return dd_dispatch32(in_dtype, [&](auto ti) {
+    return dd_dispatch32(out_dtype, [&](auto to) {
+      using TI = typename decltype(ti)::type;
+      using TO = typename decltype(to)::type;
+      hipLaunchKernelGGL((dd_fourier_embed2_kernel<TI, TO>), dim3(grid_for(rows * dims)), dim3(256), 0, dd_stream(stream),
+                         (const TI*)x, (TO*)out, rows, dims, fr, num_freqs, inc, inner, stride_outer, stride_inner,
+                         stride_dim, out_ld);
+      return dd_check_launch();
+    });
+  });
 }
 
 extern "C" int dd_box_tokens(const dd_box_tokens_desc* d, dd_stream_t stream) {
@@ -254,14 +246,12 @@ extern "C" int dd_box_tokens(const dd_box_tokens_desc* d, dd_stream_t stream) {
     return DD_ERR_BAD_ARG;
   FourierFreqs2 fr{};
   for (int i = 0; i < d->num_freqs; ++i) fr.f[i] = d->freqs[i];
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
-  const bool h = d->dtype == DD_F16;
-  switch (d->points_dtype) {
-    case DD_F16: return h ? launch_box<_Float16, _Float16>(d, fr, s) : launch_box<_Float16, __bf16>(d, fr, s);
-    case DD_BF16: return h ? launch_box<__bf16, _Float16>(d, fr, s) : launch_box<__bf16, __bf16>(d, fr, s);
-    default: return h ? launch_box<float, _Float16>(d, fr, s) : launch_box<float, __bf16>(d, fr, s);
-  }
+  return dd_dispatch32(d->points_dtype, [&](auto ti) {
+    return dd_dispatch16(d->dtype, [&](auto t) {
+      return launch_box<typename decltype(ti)::type, typename decltype(t)::type>(d, fr, dd_stream(stream));
+    });
+  });
 }
 
 extern "C" int dd_ctx_assemble(const void* cam, const void* text, const void* box, void* full, void* txt, int32_t m,
@@ -274,16 +264,13 @@ extern "C" int dd_ctx_assemble(const void* cam, const void* text, const void* bo
   if (!dd_aligned16(cam) || !dd_aligned16(text) || !dd_aligned16(full) || (box && !dd_aligned16(box)) ||
       (txt && !dd_aligned16(txt)))
     return DD_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
   const int64_t total = (int64_t)m * ((1 + lt + nbox) + (txt ? lt : 0)) * (dim / 8);
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL(dd_ctx_assemble_kernel<_Float16>, dim3(grid_for(total)), dim3(256), 0, s, (const _Float16*)cam,
-                       (const _Float16*)text, (const _Float16*)box, (_Float16*)full, (_Float16*)txt, m, n_cam, lt, nbox,
-                       dim, text_per_view ? 1 : 0, box_views);
-  else
-    hipLaunchKernelGGL(dd_ctx_assemble_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, s, (const __bf16*)cam,
-                       (const __bf16*)text, (const __bf16*)box, (__bf16*)full, (__bf16*)txt, m, n_cam, lt, nbox, dim,
-                       text_per_view ? 1 : 0, box_views);
-  return dd_check_launch();
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dd_ctx_assemble_kernel<T>, dim3(grid_for(total)), dim3(256), 0, dd_stream(stream), (const T*)cam,
+                       (const T*)text, (const T*)box, (T*)full, (T*)txt, m, n_cam, lt, nbox, dim, text_per_view ? 1 : 0,
+                       box_views);
+    return dd_check_launch();
+  });
 }

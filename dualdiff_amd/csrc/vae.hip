@@ -63,8 +63,9 @@ extern "C" int dd_vae_posterior(const void* moments, const float* wq, const floa
   if (!dd_aligned16(moments)) return DD_ERR_BAD_ARG;
   const int64_t hw = (int64_t)h * w, pixels = (int64_t)m * hw;
   if (hw >= ((int64_t)1 << 31) || (pixels + 255) / 256 >= ((int64_t)1 << 31)) return DD_ERR_UNSUPPORTED;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
-  if (dtype == DD_F16) return launch_posterior<_Float16>(moments, wq, bq, noise, z, pixels, (int32_t)hw, scale, out_f32, s);
-  return launch_posterior<__bf16>(moments, wq, bq, noise, z, pixels, (int32_t)hw, scale, out_f32, s);
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_posterior<T>(moments, wq, bq, noise, z, pixels, (int32_t)hw, scale, out_f32, dd_stream(stream));
+  });
 }

@@ -491,15 +491,13 @@ extern "C" int dd_xattn_pack_weight(const void* w, void* packed, int32_t dtype, 
   if (!w || !packed || !dd_aligned16(w) || !dd_aligned16(packed)) return DD_ERR_BAD_ARG;
   if (dtype != DD_F16 && dtype != DD_BF16) return DD_ERR_BAD_ARG;
   dd_clear_error();
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int chunks = 10 * XC * 4;
-  if (dtype == DD_F16)
-    hipLaunchKernelGGL(dd_xattn_pack_kernel<_Float16>, dim3((chunks + 255) / 256), dim3(256), 0, s,
-                       reinterpret_cast<const _Float16*>(w), reinterpret_cast<_Float16*>(packed));
-  else
-    hipLaunchKernelGGL(dd_xattn_pack_kernel<__bf16>, dim3((chunks + 255) / 256), dim3(256), 0, s,
-                       reinterpret_cast<const __bf16*>(w), reinterpret_cast<__bf16*>(packed));
-  return dd_check_launch();
+  return dd_dispatch16(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dd_xattn_pack_kernel<T>, dim3((chunks + 255) / 256), dim3(256), 0, dd_stream(stream),
+                       (const T*)w, (T*)packed);
+    return dd_check_launch();
+  });
 }
 
 extern "C" int dd_xattn320(const dd_xattn_desc* d, dd_stream_t stream) {
@@ -530,8 +528,6 @@ extern "C" int dd_xattn320(const dd_xattn_desc* d, dd_stream_t stream) {
   p.tiles = (d->rows_per_inst + XR - 1) / XR;
   p.qscale = d->scale * 1.44269504088896340736f;
   { static const int dbg = getenv("DD_XATTN_DBG") ? atoi(getenv("DD_XATTN_DBG")) : 0; p.dbg = dbg; }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dd_clear_error();
-  if (d->dtype == DD_F16) return launch_xattn<_Float16>(p, s);
-  return launch_xattn<__bf16>(p, s);
+  return dd_dispatch16(d->dtype, [&](auto t) { return launch_xattn<typename decltype(t)::type>(p, dd_stream(stream)); });
 }
