@@ -156,6 +156,9 @@ SIGNATURES = {
                                        c_int32, c_int32, c_void_p]),
     "dd_image_load_u8": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                    c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
+    "dd_box_views": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                               c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
     "dd_clip_embed": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                 c_int32, c_int32, c_void_p]),
     "dd_causal_attention": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,

@@ -490,6 +490,74 @@ def image_load_u8(frames, size, box=None, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0
     return out
 
 
+BOX_POINT_MODES = {"all-xyz": 0, "cxyz": 1}      # dataset/utils.py:222-226; points per box 8 / 4
+BOX_FILTERS = {"all": 0, "positive_z": 1, "canvas": 2}
+
+
+def box_views(corners, labels, offsets, transforms, views, cap, points_mode="all-xyz", filter_mode="positive_z",
+              canvas_size=None, filter_corners=None, out=None):
+    """Every scene's box corners -> the per-view `bboxes_3d_data` at a capacity of `cap` slots, in one launch
+    (include/dualdiff_hip.h: dd_box_views; dataset/utils.py:128-262).  corners (total, 8, 3) fp32, labels (total,) int64,
+    offsets (scenes + 1,) int32, transforms (scenes, views, 4, 4) fp32 or None for filter "all", filter_corners as
+    corners or None — all contiguous device tensors.  canvas_size = (h, w) for filter "canvas".
+    -> (bboxes (scenes, views, cap, P, 3) fp32, classes (scenes, views, cap) int64, masks (..., cap) bool, counts (scenes,
+    views) int32, max_len (1,) int32); out = the same five tensors of the caller's (e.g. the second half of a zeroed CFG
+    batch).  Nothing is read back: counts and max_len stay in device memory."""
+    what = "box_views"
+    if points_mode not in BOX_POINT_MODES:
+        raise ValueError("%s: points_mode must be one of %s, got %r" % (what, ", ".join(sorted(BOX_POINT_MODES)), points_mode))
+    if filter_mode not in BOX_FILTERS:
+        raise ValueError("%s: filter_mode must be one of %s, got %r" % (what, ", ".join(sorted(BOX_FILTERS)), filter_mode))
+    if corners.dim() != 3 or tuple(corners.shape[1:]) != (8, 3) or corners.dtype != torch.float32:
+        raise ValueError("%s takes fp32 corners (total, 8, 3), got %s %s" % (what, corners.dtype, tuple(corners.shape)))
+    total = corners.shape[0]
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (total,):
+        raise ValueError("%s takes int64 labels (%d,), got %s %s" % (what, total, labels.dtype, tuple(labels.shape)))
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.shape[0] < 2:
+        raise ValueError("%s takes int32 offsets (scenes + 1,), got %s %s" % (what, offsets.dtype, tuple(offsets.shape)))
+    scenes, views, cap = offsets.shape[0] - 1, int(views), int(cap)
+    if views <= 0 or cap <= 0:
+        raise ValueError("%s: views and cap must be positive, got %d and %d" % (what, views, cap))
+    fm = BOX_FILTERS[filter_mode]
+    if fm == 0 and views != 1:
+        raise ValueError("%s: filter \"all\" is the view-shared form and has one view, got %d" % (what, views))
+    if fm != 0 and (transforms is None or transforms.dtype != torch.float32
+                    or tuple(transforms.shape) != (scenes, views, 4, 4)):
+        raise ValueError("%s: filter %r takes fp32 transforms (%d, %d, 4, 4)" % (what, filter_mode, scenes, views))
+    ch = cw = 0
+    if fm == 2:
+        try:
+            ch, cw = (int(v) for v in canvas_size)
+        except (TypeError, ValueError):
+            raise ValueError("%s: filter \"canvas\" takes canvas_size = (h, w), got %r" % (what, canvas_size))
+        if ch <= 0 or cw <= 0:
+            raise ValueError("%s: canvas_size must be positive, got %r" % (what, canvas_size))
+    if filter_corners is not None and (filter_corners.dtype != torch.float32 or filter_corners.shape != corners.shape):
+        raise ValueError("%s: filter_corners must match corners" % what)
+    ins = (corners, labels, offsets, transforms, filter_corners)
+    if any(t is not None and not t.is_contiguous() for t in ins):
+        raise ValueError("%s takes contiguous tensors" % what)
+    _need_gpu(*ins)
+    pts = 8 if BOX_POINT_MODES[points_mode] == 0 else 4
+    shapes = ((scenes, views, cap, pts, 3), (scenes, views, cap), (scenes, views, cap), (scenes, views), (1,))
+    dtypes = (torch.float32, torch.int64, torch.bool, torch.int32, torch.int32)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=corners.device) for s, d in zip(shapes, dtypes))
+    else:
+        out = tuple(out)
+        if len(out) != 5 or any(tuple(t.shape) != s or t.dtype != d or not t.is_contiguous()
+                                for t, s, d in zip(out, shapes, dtypes)):
+            raise ValueError("%s: out must be contiguous tensors of %s" % (what, list(zip(shapes, dtypes))))
+        _need_gpu(*out)
+    lib = _native.load()
+    _timer.launch(what, lib.dd_box_views, _ptr(corners), _ptr(filter_corners), _ptr(labels), _ptr(offsets),
+                  _ptr(transforms) if fm != 0 else None, total, scenes, views, cap, BOX_POINT_MODES[points_mode], fm, ch, cw,
+                  *(_ptr(t) for t in out), _stream(),
+                  book=lambda: ("dd_box_views_kernel", 0.0,
+                                float((1 if fm == 0 else views) * total * 96 + out[0].numel() * 4 + out[1].numel() * 9)))
+    return out
+
+
 def groupnorm(x, gamma, beta, m, hw, groups, eps, silu, x2=None, out=None):
     """GroupNorm (+SiLU) over an NHWC batch; x2 = optional second source concatenated on C."""
     lib = _native.load()

@@ -500,6 +500,43 @@ int dd_image_load_u8(const uint8_t* in, void* out, int32_t m, int32_t h, int32_t
                      int32_t ksy, const float* lut, int32_t dtype, int32_t layout, dd_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Box input (csrc/boxes.hip): 3D box corners -> the per-view `bboxes_3d_data` of the reference's collate function
+ * (dataset/utils.py:128-262: per-view visibility, order-preserving selection, padding), in the layout dd_box_tokens reads.
+ *   corners        [total][8][3] fp32: the payload, every scene's boxes concatenated;
+ *   filter_corners same shape, or NULL (= corners): the corners that are transformed for the visibility test (the
+ *                  reference tests the box re-centred to (0.5, 0.5, 0.5), runner/box_visualizer.py:63);
+ *   labels         [total] int64;
+ *   offsets        [scenes + 1] int32: scene s owns boxes offsets[s] .. offsets[s + 1] (clamped to [0, total] and to
+ *                  non-decreasing by the kernel; an empty scene is legal);
+ *   transforms     [scenes][views][4][4] fp32, row-major; NULL only for filter_mode 0.
+ * points_mode 0: all 8 corners (`all-xyz`); 1: corners 6, 5, 7, 2 in that order (`cxyz`, dataset/utils.py:224).
+ * filter_mode 0: keep every box (`view_shared`; views must be 1);
+ *             1: `ensure_positive_z`: keep a box if any corner has z > 0;
+ *             2: `ensure_canvas`: zc = clip(z, 1e-5, 1e5), x /= zc, y /= zc; keep if any corner has z / |z| > 0 AND any
+ *                corner has 0 < x < canvas_w AND any corner has 0 < y < canvas_h (three independent "any").
+ * (x, y, z) = rows 0..2 of  matrix (promoted to double) * (corner promoted to double, 1.0), float64 with IEEE division as
+ * in runner/box_visualizer.py:71-85; the order of the four-term sums is the kernel's (fused multiply-adds from the
+ * translation column on), so a quantity within rounding of its threshold may decide differently than another summation.
+ * Out, for every (scene, view), rows of `cap` slots and P = 8 or 4 points:
+ *   bboxes  [scenes][views][cap][P][3] fp32: the kept boxes' payload points in their original order, then zeros;
+ *   classes [scenes][views][cap] int64: their labels, then -1;
+ *   masks   [scenes][views][cap] bytes: 1 for a kept box, then 0;
+ *   counts  [scenes][views] int32: the number kept, also when it exceeds cap (the boxes beyond cap are dropped);
+ *   max_len [1] int32: the largest count of this launch, whatever it held before (cleared on the stream, then a vector
+ *           atomic max per workgroup).
+ * Every slot below cap is written and nothing at or past it.  Pointers need their element's alignment only (4 bytes for
+ * the fp32 / int32 arrays, 8 for the int64 ones); rows move as 16-byte vectors where the base allows it.
+ * DD_ERR_BAD_ARG, decided before the first runtime call: a NULL required pointer (corners / labels may be NULL when
+ * total == 0), total < 0, non-positive scenes / views / cap, an unknown mode, filter_mode 0 with views != 1, filter_mode
+ * 1 or 2 without transforms, filter_mode 2 with a non-positive canvas, a misaligned pointer.  scenes * views >= 2^31 or
+ * scenes * views * cap >= 2^40: DD_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------- */
+int dd_box_views(const float* corners, const float* filter_corners, const int64_t* labels, const int32_t* offsets,
+                 const float* transforms, int32_t total, int32_t scenes, int32_t views, int32_t cap,
+                 int32_t points_mode, int32_t filter_mode, int32_t canvas_h, int32_t canvas_w, float* bboxes,
+                 int64_t* classes, uint8_t* masks, int32_t* counts, int32_t* max_len, dd_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * CLIP text encoder (csrc/clip.hip): the SD-v1.5 `text_encoder` (transformers.CLIPTextModel) that the reference calls at
  * runner/base_runner.py:119,511-514, runner/multiview_runner.py:145,427-428 (`text_encoder(ids)[0]`), through diffusers'
  * _encode_prompt at pipeline/pipeline_bev_controlnet.py:273 and at networks/bbox_embedder.py:133-145
