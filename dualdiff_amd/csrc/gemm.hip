@@ -1,7 +1,8 @@
 // GEMM / conv host side: the planner over the tile table (gemm_tiles.h), the split-K reduce, and the C entry points.
-// The kernels are in the family translation units (gemm1.hip, gemm23.hip, gemm2_geglu.hip, gemm2_conv.hip, gemm4.hip, conv3s.hip).
+// The kernels are in the family translation units (gemm1.hip, gemm23.hip, gemm2_geglu.hip, gemm2_conv.hip, gemm2_upfold.hip, gemm4.hip, conv3s.hip).
 #include "gemm_device.h"
 #include <algorithm>
+#include <cmath>
 
 namespace {
 
@@ -41,6 +42,69 @@ bool dma_ok(const dd_gemm_desc* d) {
     if (d->a2) ok = ok && (d->k1 % BK) == 0 && (int64_t)d->rows * d->lda2 < lim;
   }
   return ok;
+}
+
+// ---- folded-upsample conv (dd_gemm_desc.upfold): the classes of the output coordinates of one axis -------------------
+// torch nearest, as the 9-tap kernels compute it: min(floor(dst * (float)(in / out)), in - 1)
+int upfold_src(int o, int in, int out) { return std::min((int)floorf((float)o * ((float)in / (float)out)), in - 1); }
+
+// Class of output coordinate o (UpfoldTab), or -1 where no class reproduces its three taps.  Slot 0 / 1 of class 0 and 2
+// reads source s - 1 / s and of class 1 s / s + 1, s = src(o); the taps go to slots (0 | 1 1), (0 0 | 1), (0 | 1 | dropped).
+// A tap inside the output must find its own source in its slot; a tap outside it (zero padding) must be dropped or sit in a
+// slot outside the source image, which the DMA fills with zeros.
+int upfold_class(int o, int in, int out) {
+  const int s = upfold_src(o, in, out);
+  for (int c = 0; c < 3; ++c) {
+    bool ok = true;
+    for (int t = -1; t <= 1 && ok; ++t) {
+      const bool tap_in = o + t >= 0 && o + t < out;
+      if (c == 2 && t == 1) { ok = !tap_in; continue; }
+      const int src = (c == 1 ? s : s - 1) + (c == 1 ? t == 1 : t >= 0);
+      const bool src_in = src >= 0 && src < in;
+      ok = tap_in ? src_in && upfold_src(o + t, in, out) == src : !src_in;
+    }
+    if (ok) return c;
+  }
+  return -1;
+}
+
+// the coordinates of an axis class by class; false where the fold does not apply
+bool upfold_axis(int in, int out, uint8_t* list, uint8_t* n, uint8_t* start) {
+  if (in <= 0 || out <= in || out > kUpfoldMax) return false;
+  int pos = 0;
+  for (int c = 0; c < 3; ++c) {
+    start[c] = (uint8_t)pos;
+    for (int o = 0; o < out; ++o) {
+      const int k = upfold_class(o, in, out);
+      if (k < 0) return false;
+      if (k == c) list[pos++] = (uint8_t)o;
+    }
+    n[c] = (uint8_t)(pos - start[c]);
+  }
+  return true;
+}
+
+// the class table of a descriptor for row tiles of bm rows; false where the fold does not apply
+bool upfold_tab(const dd_gemm_desc* d, int bm, UpfoldTab* t, int* tiles_m, int* ncls) {
+  *t = UpfoldTab{};
+  if (!d->conv || d->stride != 1 || d->hout != d->hv || d->wout != d->wv || d->hout <= 0 || d->wout <= 0) return false;
+  if (!upfold_axis(d->hin, d->hv, t->y, t->ny, t->y0) || !upfold_axis(d->win, d->wv, t->x, t->nx, t->x0)) return false;
+  t->m = d->rows / (d->hout * d->wout);
+  int tiles = 0, w = 0;
+  for (int c = 0; c < 9; ++c) {
+    const int plane = t->ny[c / 3] * t->nx[c % 3];
+    t->tile0[c] = (uint16_t)tiles;
+    t->widx[c] = (uint8_t)w;
+    t->inv_plane[c] = plane ? 1.0f / (float)plane : 1.0f;
+    if (plane) ++w;
+    tiles += (t->m * plane + bm - 1) / bm;
+    if (tiles > 65535) return false;
+  }
+  t->tile0[9] = (uint16_t)tiles;
+  for (int c = 0; c < 3; ++c) t->inv_nx[c] = t->nx[c] ? 1.0f / (float)t->nx[c] : 1.0f;
+  *tiles_m = tiles;
+  *ncls = w;
+  return true;
 }
 
 // DD_PERSIST=0 / DD_PERSIST3=0: the A/B switches of the two persistent forms, read once
@@ -95,7 +159,7 @@ Plan plan_direct(const dd_gemm_desc* d, int ti, unsigned form) {
 
 // the form a descriptor asks for; pad_lo == 0 is F_PAD0 (validate_pad: conv, stride 2, no upsample, no GEGLU)
 unsigned form_of(const dd_gemm_desc* d, int pad_lo) {
-  return pad_lo == 0 ? F_PAD0 : d->conv ? F_CONV : d->epilogue == DD_EPI_GEGLU ? F_GEGLU : F_DENSE;
+  return pad_lo == 0 ? F_PAD0 : d->conv && d->upfold ? F_UPFOLD : d->conv ? F_CONV : d->epilogue == DD_EPI_GEGLU ? F_GEGLU : F_DENSE;
 }
 
 Plan make_plan(const dd_gemm_desc* d, int pad_lo) {
@@ -111,6 +175,11 @@ Plan make_plan(const dd_gemm_desc* d, int pad_lo) {
       const int bn_out = geglu ? tile_bn(t) / 2 : tile_bn(t);
       if ((long)ceil_div(d->rows, tile_bm(t)) * ceil_div(d->n, bn_out) >= (long)kNumCU * 3 / 2) break;
     }
+  }
+  if (ti < 0) {
+    if (form != F_UPFOLD) return unsupported();
+    // no tile named (a direct caller with the tuner off): the model folds only shapes of the tracked table, with their tile
+    ti = tile_index(d->rows >= 8192 ? 28 : 52);
   }
   if (d->ln_colsum) {                                // LayerNorm fold lives in the LDS-DMA family only
     // heuristic picked a register-staged tile: take its LDS-DMA twin (round 5 removed the 2-slot 128x64 / 64x64 tiles the
@@ -133,6 +202,8 @@ Plan make_plan(const dd_gemm_desc* d, int pad_lo) {
     if (d->n != 320 || !dma_ok(d)) return unsupported();
   }
   if (kTiles[ti].family == FAM_DIRECT) return plan_direct(d, ti, form);
+  // the folded-upsample conv: no other family has the form, and its epilogue is the plain T store
+  if (form == F_UPFOLD && (kTiles[ti].family != FAM_RING || !dma_ok(d) || d->ln_stats_out || d->out_f32)) return unsupported();
   if (kTiles[ti].family != FAM_REG && !dma_ok(d)) {  // same tile shape, register-staged family
     const int reg = twin(kTiles[ti], FAM_REG);       // no twin: 128x128 (GEGLU-capable) / 64x64
     ti = reg >= 0 ? reg : tile_index(geglu ? kTile128x128 : kTile64x64);
@@ -146,6 +217,11 @@ Plan make_plan(const dd_gemm_desc* d, int pad_lo) {
   pl.tile_idx = ti;
   pl.tiles_m = ceil_div(d->rows, tile_bm(t));
   pl.tiles_n = ceil_div(d->n, bn_out);
+  if (form == F_UPFOLD) {                            // row tiles class by class; one [n][k] weight matrix per class
+    int ncls = 0;
+    if (!upfold_tab(d, tile_bm(t), &pl.upf, &pl.tiles_m, &ncls) || (int64_t)ncls * d->n * d->k >= ((int64_t)1 << 30))
+      return unsupported();
+  }
   int split = d->split_k;
   const int nkt = ceil_div(d->k, BK);
   if (split <= 0) {                                  // auto: two waves of workgroups, at least 4 K-steps each, at most 32 slabs
@@ -182,7 +258,7 @@ inline bool gemm4_takes(const Plan& pl) {          // the persistent form: more 
 LaunchFn* launcher(const Plan& pl, unsigned form) {     // the translation unit that holds the tile's kernel in this form
   switch (kTiles[pl.tile_idx].family) {
     case FAM_REG: return launch_gemm1;
-    case FAM_RING: return form == F_CONV ? launch_gemm2_conv : form == F_GEGLU ? launch_gemm2_geglu : launch_gemm2_dense;
+    case FAM_RING: return form == F_UPFOLD ? launch_gemm2_upfold : form == F_CONV ? launch_gemm2_conv : form == F_GEGLU ? launch_gemm2_geglu : launch_gemm2_dense;
     case FAM_PIPE: return gemm4_takes(pl) ? launch_gemm4 : launch_gemm3;
     default: return launch_conv3s;
   }
@@ -214,7 +290,7 @@ int validate(const dd_gemm_desc* d, int pad_lo = 1) {
   if (d->rowvec && (!dd_aligned16(d->rowvec) || (d->ld_rowvec & 7) || d->rows_per_inst <= 0)) return DD_ERR_BAD_ARG;
   if (d->conv) {
     if (d->a2) return DD_ERR_UNSUPPORTED;
-    if (d->cin <= 0 || (d->cin & 7) || d->k != 9 * d->cin) return DD_ERR_BAD_ARG;
+    if (d->cin <= 0 || (d->cin & 7) || d->k != (d->upfold ? 4 : 9) * d->cin) return DD_ERR_BAD_ARG;
     if (d->hin <= 0 || d->win <= 0 || d->hout <= 0 || d->wout <= 0) return DD_ERR_BAD_ARG;
     if (d->stride != 1 && d->stride != 2) return DD_ERR_UNSUPPORTED;
     if (d->hv <= 0 || d->wv <= 0) return DD_ERR_BAD_ARG;
@@ -238,6 +314,7 @@ int validate(const dd_gemm_desc* d, int pad_lo = 1) {
   }
   if (d->epilogue == DD_EPI_GEGLU && (d->res || d->rowvec || d->accumulate || d->alpha != 1.0f)) return DD_ERR_UNSUPPORTED;
   if (d->epilogue == DD_EPI_GEGLU && d->conv) return DD_ERR_UNSUPPORTED;      // no tile carries a conv + GEGLU kernel
+  if (d->upfold && (!d->conv || pad_lo != 1)) return DD_ERR_BAD_ARG;         // (whether the map folds is the planner's answer)
   return DD_OK;
 }
 
@@ -291,6 +368,9 @@ const char* kernel_name(const dd_gemm_desc* d, int pad_lo) {
   } else if (t.family == FAM_PIPE) {
     kern = gemm4_takes(pl) ? "dd_gemm4_kernel" : "dd_gemm3_kernel";
     snprintf(args, sizeof(args), ", %d, %s", t.depth, geglu);
+  } else if (t.family == FAM_RING && d->upfold) {
+    kern = "dd_gemm2u_kernel";
+    snprintf(args, sizeof(args), ", %d", t.depth);
   } else if (t.family == FAM_RING) {
     kern = "dd_gemm2_kernel";
     snprintf(args, sizeof(args), ", %d, %s, %s", t.depth, conv, geglu);
@@ -340,6 +420,11 @@ int gemm_run(const dd_gemm_desc* d, int pad_lo, dd_stream_t stream) {
   {
     const int64_t nw = (d->epilogue == DD_EPI_GEGLU ? 2 : 1) * (int64_t)d->n;
     p.w_bytes = (uint32_t)(nw * d->k * 2);
+    if (d->upfold) {                                   // one matrix per non-empty class
+      int ncls = 0;
+      for (int c = 0; c < 9; ++c) ncls += pl.upf.tile0[c + 1] > pl.upf.tile0[c];
+      p.w_bytes = (uint32_t)(ncls * nw * d->k * 2);
+    }
     if (d->conv) {
       p.a_bytes = (uint32_t)((int64_t)d->rows / (d->hout * d->wout) * d->hin * d->win * d->cin * 2);
       p.a2_bytes = 0;

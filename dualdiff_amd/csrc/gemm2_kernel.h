@@ -7,7 +7,7 @@
 //  * counted s_waitcnt vmcnt(N) + raw s_barrier: one barrier per K-step, loads stay in flight
 //    across it.
 // =============================================================================================
-// Compiled by three translation units, one per form (gemm23.hip for the dense one, gemm2_geglu.hip, gemm2_conv.hip): this kernel is
+// Compiled by four translation units, one per form (gemm23.hip for the dense one, gemm2_geglu.hip, gemm2_conv.hip, gemm2_upfold.hip): this kernel is
 // more than half of the library's device code, and one unit of it would be the whole build's critical path.
 #pragma once
 #include "gemm_device.h"
@@ -23,9 +23,11 @@ constexpr int gemm2_min_blocks() {
   return (!CONV && NW == 4 && TM * TN <= 8 && NSTAGE <= 3) ? 2 : 1;
 }
 
-template <typename T, int WAVES_M, int WAVES_N, int TM, int TN, int NSTAGE, bool CONV, bool GEGLU>
-__global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (gemm2_min_blocks<WAVES_M * WAVES_N, TM, TN, NSTAGE, CONV>()))
-void dd_gemm2_kernel(const GemmParams p) {
+// The body of dd_gemm2_kernel and of dd_gemm2u_kernel (UPF: the folded-upsample conv, `u` its class table — CONV with
+// 2 x 2 summed taps per output pixel, K = 4 * cin, and the rows of a tile taken from one class of output pixels).
+template <typename T, int WAVES_M, int WAVES_N, int TM, int TN, int NSTAGE, bool CONV, bool GEGLU, bool UPF>
+__device__ __forceinline__ void dd_gemm2_body(const GemmParams& p, const UpfoldTab* u) {
+  static_assert(!UPF || (CONV && !GEGLU), "the folded upsample is a conv form");
   using V8 = typename dd_vec<T>::v8;
   constexpr int NW = WAVES_M * WAVES_N;
   constexpr int BM = WAVES_M * TM * 16;
@@ -62,6 +64,39 @@ void dd_gemm2_kernel(const GemmParams p) {
   int tile = xcd_remap(lin, ntiles);
   int block_m0 = (tile / p.tiles_n) * BM;
   int block_n0 = (tile % p.tiles_n) * BN_OUT;
+  // UPF: the class of this row tile (all scalar); block_m0 counts the rows of that class
+  int u_rc = 0, u_cc = 0, u_widx = 0, u_ny = 1, u_nx = 1, u_y0 = 0, u_x0 = 0, u_rows = 0;
+  float u_inv_plane = 1.f, u_inv_nx = 1.f;
+  if constexpr (UPF) {
+    const int tmi = tile / p.tiles_n;
+    int cls = 0;
+#pragma unroll
+    for (int c = 1; c < 9; ++c) if (tmi >= (int)u->tile0[c]) cls = c;
+    int t0 = 0;
+#pragma unroll
+    for (int c = 0; c < 9; ++c)
+      if (c == cls) { t0 = u->tile0[c]; u_widx = u->widx[c]; u_inv_plane = u->inv_plane[c]; }
+    u_rc = (cls * 11) >> 5;                          // cls / 3
+    u_cc = cls - u_rc * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (c == u_rc) { u_ny = u->ny[c]; u_y0 = u->y0[c]; }
+      if (c == u_cc) { u_nx = u->nx[c]; u_x0 = u->x0[c]; u_inv_nx = u->inv_nx[c]; }
+    }
+    u_rows = u->m * u_ny * u_nx;
+    block_m0 = (tmi - t0) * BM;
+  }
+  // UPF: tile row r of the class -> instance, output y, output x (false: a padding row past the class's end)
+  auto u_pixel = [&](const int r, int& inst, int& oy, int& ox) __attribute__((always_inline)) {
+    const bool rv = r < u_rows;
+    const int rr = rv ? r : 0;
+    inst = dd_fdiv(rr, u_inv_plane);
+    const int rem = rr - inst * (u_ny * u_nx);
+    const int iy = dd_fdiv(rem, u_inv_nx);
+    oy = u->y[u_y0 + iy];
+    ox = u->x[u_x0 + rem - iy * u_nx];
+    return rv;
+  };
 
   const int kbeg = blockIdx.z * p.k_per_split;
   const int kend = min(p.k, kbeg + p.k_per_split);
@@ -99,7 +134,7 @@ void dd_gemm2_kernel(const GemmParams p) {
       const int col = bn0 + loc;
       n_glob = (col < p.n) ? col : -1;
     }
-    wv[j] = n_glob >= 0 ? (uint32_t)n_glob * (uint32_t)p.k * 2u + lcb : DD_OOB;
+    wv[j] = n_glob >= 0 ? (uint32_t)(UPF ? u_widx * p.n + n_glob : n_glob) * (uint32_t)p.k * 2u + lcb : DD_OOB;
   }
   };
   make_wv(block_n0);
@@ -110,8 +145,33 @@ void dd_gemm2_kernel(const GemmParams p) {
 #pragma unroll
   for (int j = 0; j < XI; ++j) {
     const int r = block_m0 + (j * NW + wave) * 8 + lrow;
-    const bool rv = r < p.rows;
-    if (CONV) {
+    [[maybe_unused]] const bool rv = r < p.rows;        // (UPF: a row is valid by its class, u_pixel)
+    if constexpr (UPF) {
+      // slot 0 / 1 of an axis reads source s - 1 / s (classes 0, 2) or s / s + 1 (class 1), s = src(o); a slot outside the
+      // image gets the out-of-range offset like any padding tap
+      int inst, oy, ox;
+      const bool uv = u_pixel(r, inst, oy, ox);
+      const int sy0 = min((int)floorf(oy * p.scale_h), p.hin - 1) - (u_rc != 1);
+      const int sx0 = min((int)floorf(ox * p.scale_w), p.win - 1) - (u_cc != 1);
+      uint32_t bits = 0;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int iy = sy0 + t, ix = sx0 + t;
+        const bool vy = iy >= 0 && iy < p.hin, vx = ix >= 0 && ix < p.win;
+        const int sy = min(max(iy, 0), p.hin - 1), sx = min(max(ix, 0), p.win - 1);
+        syo[j][t] = (uint32_t)((inst * p.hin + sy) * p.win) * (uint32_t)p.cin * 2u + lcb;
+        sxo[j][t] = (uint32_t)(sx * p.cin) * 2u;
+        if (vy) bits |= 1u << t;
+        if (vx) bits |= 4u << t;
+      }
+      syo[j][2] = sxo[j][2] = 0;
+      uint32_t m4 = 0;                                // bit (sy*2+sx): slot reads a real pixel
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        if (uv && ((bits >> (t >> 1)) & 1u) && ((bits >> (2 + (t & 1))) & 1u)) m4 |= 1u << t;
+      xbits[j] = m4;
+      xe[j] = DD_OOB;
+    } else if (CONV) {
       const int hw = p.hout * p.wout;
       const int rr = rv ? r : 0;
       const int inst = dd_fdiv(rr, p.inv_hw);
@@ -158,8 +218,8 @@ void dd_gemm2_kernel(const GemmParams p) {
   // would force the tables to scratch)
   auto set_tap = [&](int tap) __attribute__((always_inline)) {
     if (CONV) {
-      const int ky = (tap * 11) >> 5;                 // tap / 3 for tap in [0, 9]
-      const int kx = tap - ky * 3;
+      const int ky = UPF ? tap >> 1 : (tap * 11) >> 5;         // tap / 3 for tap in [0, 9]; UPF: slot / 2 for slot in [0, 4]
+      const int kx = UPF ? tap & 1 : tap - ky * 3;
       const uint32_t y0 = 0u - (uint32_t)(ky == 0), y1 = 0u - (uint32_t)(ky == 1), y2 = 0u - (uint32_t)(ky == 2);
       const uint32_t x0 = 0u - (uint32_t)(kx == 0), x1 = 0u - (uint32_t)(kx == 1), x2 = 0u - (uint32_t)(kx == 2);
 #pragma unroll
@@ -356,6 +416,17 @@ void dd_gemm2_kernel(const GemmParams p) {
     }
   }
   const bool ln = !CONV && p.ln_colsum;
+  if constexpr (UPF) {                    // rows go to their output pixels; padding rows nowhere
+    int rowmap[TM];
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm) {
+      int inst, oy, ox;
+      const bool uv = u_pixel(block_m0 + wave_m * (TM * 16) + tm * 16 + (lane & 15), inst, oy, ox);
+      rowmap[tm] = uv ? (inst * p.hout + oy) * p.wout + ox : p.rows;
+    }
+    store_tile<T, TM, TN, false, true>(p, acc, block_m0, block_n0, wave_m, wave_n, lane, p.rows, nullptr, nullptr, rowmap);
+    break;                                // (no persistent walk in the conv forms)
+  }
   store_tile<T, TM, TN, GEGLU>(p, acc, block_m0, block_n0, wave_m, wave_n, lane, p.rows,
                                ln ? s_ln_mean : nullptr, ln ? s_ln_rstd : nullptr);
   if (!have_next) break;
@@ -370,6 +441,18 @@ void dd_gemm2_kernel(const GemmParams p) {
     for (int j = 0; j < TM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   DD_STAMP_FLUSH(p);
+}
+
+template <typename T, int WAVES_M, int WAVES_N, int TM, int TN, int NSTAGE, bool CONV, bool GEGLU>
+__global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (gemm2_min_blocks<WAVES_M * WAVES_N, TM, TN, NSTAGE, CONV>()))
+void dd_gemm2_kernel(const GemmParams p) {
+  dd_gemm2_body<T, WAVES_M, WAVES_N, TM, TN, NSTAGE, CONV, GEGLU, false>(p, nullptr);
+}
+
+template <typename T, int WAVES_M, int WAVES_N, int TM, int TN, int NSTAGE>
+__global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (gemm2_min_blocks<WAVES_M * WAVES_N, TM, TN, NSTAGE, true>()))
+void dd_gemm2u_kernel(const GemmParams p, const UpfoldTab u) {
+  dd_gemm2_body<T, WAVES_M, WAVES_N, TM, TN, NSTAGE, true, false, true>(p, &u);
 }
 
 struct Gemm2 {
@@ -398,6 +481,22 @@ struct Gemm2 {
       }
     }
     return launch_kernel<kern>(grid, 64 * t.wm * t.wn, smem, s, q);
+  }
+};
+
+
+struct Gemm2U {
+  static constexpr Family family = FAM_RING;
+  static constexpr unsigned needs = 0;
+  template <typename T, size_t I, unsigned FORM>
+  static int run(const GemmParams& p, const Plan& pl, hipStream_t s) {
+    constexpr const TileCfg& t = kTiles[I];
+    constexpr size_t smem = (size_t)t.depth * (tile_bm(t) + tile_bn(t)) * BK * sizeof(T);
+    static_assert(smem <= 160 * 1024, "LDS");
+    constexpr auto kern = dd_gemm2u_kernel<T, t.wm, t.wn, t.tm, t.tn, t.depth>;
+    raise_lds_limit<kern>(smem);
+    hipLaunchKernelGGL(kern, dim3(pl.tiles_m * pl.tiles_n, 1, pl.split), dim3(64 * t.wm * t.wn), smem, s, p, pl.upf);
+    return dd_check_launch();
   }
 };
 

@@ -19,7 +19,7 @@
 //  * split-K for the deep, weight-bound levels (336..1092 rows x K up to 23040).
 //
 // This header: the device helpers every kernel family shares (epilogues, LDS-DMA primitives).  The families live in
-// gemm1.hip, gemm2_kernel.h (+ gemm23 / gemm2_geglu / gemm2_conv.hip), gemm3_kernel.h, gemm4.hip and conv3s.hip; the tile
+// gemm1.hip, gemm2_kernel.h (+ gemm23 / gemm2_geglu / gemm2_conv / gemm2_upfold.hip), gemm3_kernel.h, gemm4.hip and conv3s.hip; the tile
 // table and the dispatch in gemm_tiles.h; the planner, the split-K reduce and the C entry points in gemm.hip.
 #pragma once
 #include "dd_common.h"
@@ -111,10 +111,14 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 // Every global read of the epilogue (bias, time-embedding vector, residual, accumulate target) is
 // issued before the stores of its row batch: `out` may alias `res`, so a load placed after a store could
 // not be hoisted by the compiler and the tile would pay one memory round trip per 8-column group.
-template <typename T, int TM, int TN, bool GEGLU>
+// MAPPED (the folded-upsample conv): tile row tm*16 + (lane & 15) of the wave goes to output row rowmap[tm]; a row that is
+// not stored has rowmap[tm] >= row_end.
+template <typename T, int TM, int TN, bool GEGLU, bool MAPPED = false>
 __device__ __forceinline__ void store_tile(const GemmParams& p, f32x4 (&acc)[TN][TM], int block_m0,
                                            int block_n0, int wave_m, int wave_n, int lane, int row_end,
-                                           const float* ln_mean = nullptr, const float* ln_rstd = nullptr) {
+                                           const float* ln_mean = nullptr, const float* ln_rstd = nullptr,
+                                           const int* rowmap = nullptr) {
+  static_assert(!(MAPPED && GEGLU), "no mapped GEGLU epilogue");
   const int q = lane >> 4;
   const int c = lane & 15;
   const int row0 = block_m0 + wave_m * (TM * 16) + c;
@@ -192,7 +196,7 @@ __device__ __forceinline__ void store_tile(const GemmParams& p, f32x4 (&acc)[TN]
       // shapes, and removed in round 5: profiles/r03_splitk_inkernel_ab.txt.)
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm) {
-        const int row = row0 + tm * 16;
+        const int row = MAPPED ? rowmap[tm] : row0 + tm * 16;
         if (row >= row_end) continue;
 #pragma unroll
         for (int g8 = 0; g8 < NG; ++g8) {
@@ -232,7 +236,7 @@ __device__ __forceinline__ void store_tile(const GemmParams& p, f32x4 (&acc)[TN]
       u32x4 rv[TMB][NG], rr[TMB][NG], ra[TMB][NG];
 #pragma unroll
       for (int t2 = 0; t2 < TMB; ++t2) {
-        const int rowc = min(row0 + (tb + t2) * 16, p.rows - 1);
+        const int rowc = min(MAPPED ? rowmap[tb + t2] : row0 + (tb + t2) * 16, p.rows - 1);
         if (p.rowvec) {
           const int inst = dd_fdiv(rowc, p.inv_rpi);
 #pragma unroll
@@ -254,7 +258,7 @@ __device__ __forceinline__ void store_tile(const GemmParams& p, f32x4 (&acc)[TN]
 #pragma unroll
       for (int t2 = 0; t2 < TMB; ++t2) {
         const int tm = tb + t2;
-        const int row = row0 + tm * 16;
+        const int row = MAPPED ? rowmap[tm] : row0 + tm * 16;
         float st_s = 0.f, st_q = 0.f;                      // row statistics of this lane's columns
         if (row < row_end) {
 #pragma unroll

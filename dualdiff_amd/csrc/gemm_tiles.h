@@ -45,6 +45,20 @@ struct GemmParams {
   uint32_t ln_out_bytes;                 // ... extent of ln_out for its buffer stores
 };
 
+// Folded-upsample conv (dd_gemm2u_kernel): the output pixels of a nearest-upsample + 3x3 conv, enumerated class by class.
+// Per axis a coordinate o with s = src(o) is of class 0 (taps read s-1 | s s), 1 (s s | s+1) or 2 (s-1 | s, tap +1 outside
+// the output: the last coordinate of an odd size); a pixel's class is 3 * row class + column class, each class has its own
+// [n][4 * cin] weight matrix (the tap slices that read one source pixel summed ahead of time) and starts on a tile boundary.
+constexpr int kUpfoldMax = 64;             // largest output height / width the coordinate lists hold
+struct UpfoldTab {
+  uint16_t tile0[10];                      // first row tile of class c; [9] = all row tiles
+  uint8_t widx[9];                         // weight matrix of class c (the non-empty classes, in order)
+  uint8_t ny[3], nx[3], y0[3], x0[3];      // per axis class: coordinates, and where its list starts in y[] / x[]
+  float inv_plane[9], inv_nx[3];           // 1 / (ny * nx), 1 / nx for dd_fdiv
+  int m;                                   // instances
+  uint8_t y[kUpfoldMax], x[kUpfoldMax];    // output coordinates, class by class
+};
+
 enum Family {
   FAM_REG,      // register-staged software pipeline: dd_gemm_kernel / dd_gemm_pad0_kernel (gemm1.hip)
   FAM_RING,     // LDS-DMA ring: dd_gemm2_kernel (gemm2_kernel.h)
@@ -60,6 +74,7 @@ enum Form : unsigned {
   F_PAD0 = 8,       // conv with pad_lo = 0 (dd_gemm_conv_pad): dd_gemm_pad0_kernel
   F_LN_OUT = 16,    // the whole-row tile whose epilogue can emit LayerNorm(out) as a second tensor (dd_gemm_desc.ln_out)
   F_PERSIST = 32,   // persistent walk over the tiles: inside dd_gemm2_kernel (FAM_RING), dd_gemm4_kernel (FAM_PIPE)
+  F_UPFOLD = 64,    // folded-upsample conv (dd_gemm_desc.upfold): dd_gemm2u_kernel, the CONV ring with 2 x 2 summed taps
 };
 
 struct TileCfg {
@@ -74,6 +89,7 @@ struct TileCfg {
 constexpr unsigned REG_ALL = F_DENSE | F_CONV | F_GEGLU | F_PAD0, REG_TN2 = F_DENSE | F_CONV | F_PAD0;
 constexpr unsigned RING_ALL = F_DENSE | F_CONV | F_GEGLU | F_PERSIST, RING_TN2 = F_DENSE | F_CONV | F_PERSIST;
 constexpr unsigned RING_DENSE = F_DENSE | F_PERSIST;
+constexpr unsigned UPF = F_UPFOLD;
 constexpr unsigned PIPE = F_DENSE | F_PERSIST;
 
 // {id, name, family, waves, blocks per wave, forms[, ring slots[, GRP[, BAND]]]}
@@ -84,19 +100,19 @@ constexpr TileCfg kTiles[] = {
     {4, "64x64", FAM_REG, 2, 2, 2, 2, REG_TN2},
     {5, "256x128", FAM_REG, 4, 2, 4, 4, REG_ALL},
     {11, "128x128/dma2", FAM_RING, 2, 2, 4, 4, RING_ALL, 2},
-    {12, "128x128/dma3", FAM_RING, 2, 2, 4, 4, RING_ALL, 3},
-    {13, "128x64/dma3", FAM_RING, 2, 2, 4, 2, RING_TN2, 3},
-    {14, "64x128/dma3", FAM_RING, 2, 2, 2, 4, RING_ALL, 3},
-    {15, "64x64/dma3", FAM_RING, 2, 2, 2, 2, RING_TN2, 3},
+    {12, "128x128/dma3", FAM_RING, 2, 2, 4, 4, RING_ALL | UPF, 3},
+    {13, "128x64/dma3", FAM_RING, 2, 2, 4, 2, RING_TN2 | UPF, 3},
+    {14, "64x128/dma3", FAM_RING, 2, 2, 2, 4, RING_ALL | UPF, 3},
+    {15, "64x64/dma3", FAM_RING, 2, 2, 2, 2, RING_TN2 | UPF, 3},
     {16, "256x128/dma2", FAM_RING, 4, 2, 4, 4, RING_ALL, 2},
-    {20, "256x128/dma3", FAM_RING, 4, 2, 4, 4, RING_ALL, 3},
+    {20, "256x128/dma3", FAM_RING, 4, 2, 4, 4, RING_ALL | UPF, 3},
     {23, "128x64/dma4", FAM_RING, 2, 2, 4, 2, RING_TN2, 4},
     {24, "64x128/dma4", FAM_RING, 2, 2, 2, 4, RING_ALL, 4},
     // 160-wide tiles (10 waves = 2 x 5): every channel count of this network (320, 640, 960, 1280, 1920, 2560) is
     // a multiple of 160, so no column of the tile multiplies padding (a 128-wide tile wastes 1/6 of its MFMAs at
     // N = 320 and 16800 rows / 160 = 105 row tiles x 2 = 210 workgroups fill the chip in ONE generation)
     {27, "160x160/dma2", FAM_RING, 2, 5, 5, 2, RING_TN2, 2},
-    {28, "160x160/dma3", FAM_RING, 2, 5, 5, 2, RING_TN2, 3},
+    {28, "160x160/dma3", FAM_RING, 2, 5, 5, 2, RING_TN2 | UPF, 3},
     // 80 WHOLE rows of a 320-wide output per workgroup (1 x 10 waves): the only tile whose epilogue can emit
     // LayerNorm(out) as a second tensor (dd_gemm_desc.ln_out); 16800 rows -> 210 workgroups, one generation
     {40, "80x320/dma2", FAM_RING, 1, 10, 5, 2, RING_DENSE | F_LN_OUT, 2},
@@ -105,7 +121,7 @@ constexpr TileCfg kTiles[] = {
     // (bench.py --challenge-tiles 52, cold weights, 3 % to win): takes 28 of the dense shapes per dtype, ~1 us each
     // (1092x1280x1280 15.4 -> 14.4, 336x1280x1280 14.8 -> 13.8 and no split-K, 4200x640x1920 27.1 -> 21.7); 96x128
     // tiles won nothing (profiles/r03_tile_challenge.txt)
-    {52, "96x64/dma3", FAM_RING, 2, 2, 3, 2, RING_TN2, 3},
+    {52, "96x64/dma3", FAM_RING, 2, 2, 3, 2, RING_TN2 | UPF, 3},
     // 32-row tiles for the few-row GEMMs (time / box / text embeddings: 12-240 rows; 336 x 1280 -> 11 x 20 workgroups):
     // 1-2 us each in the same challenge; 96x64 with 2 / 4 slots, 96x128 and 192x64 tiles won nothing and were removed
     {59, "32x64/dma3", FAM_RING, 2, 2, 1, 2, RING_DENSE, 3},
@@ -113,7 +129,7 @@ constexpr TileCfg kTiles[] = {
     // 192 rows: 1092 rows -> 6 row tiles (180 workgroups at N = 3840 where 256x128 has 150): the per-CU staging rate,
     // not the tile's arithmetic intensity, bounds a launch that leaves CUs without a workgroup (1092x3840x1280:
     // 26.5 -> 23.2 us cold, 1092x1280x6400: 41.4 -> 37.6)
-    {44, "192x128/dma3", FAM_RING, 4, 2, 3, 4, RING_ALL, 3},
+    {44, "192x128/dma3", FAM_RING, 4, 2, 3, 4, RING_ALL | UPF, 3},
     {46, "192x128/dma2", FAM_RING, 4, 2, 3, 4, RING_ALL, 2},
     // 256x256 (round 3): the tiled family is bound by L2 -> LDS staging, and staged bytes per flop go with
     // (BM + BN) / (BM * BN): 0.0078 B/flop against 0.0117 for 256x128.  8 waves of 128 x 64 (32 accumulator blocks per
@@ -156,7 +172,7 @@ constexpr int tile_index(int id) {
 constexpr bool tiles_consistent() {          // what the kernels' own static_asserts do not say
   for (const TileCfg& t : kTiles)
     if (((t.forms & F_PAD0) && t.family != FAM_REG) || ((t.forms & F_CONV) && t.family == FAM_PIPE) ||
-        ((t.forms & F_LN_OUT) && tile_bn(t) != 320) || (t.family == FAM_DIRECT) != (t.forms == F_CONV)) return false;
+        ((t.forms & F_LN_OUT) && tile_bn(t) != 320) || ((t.forms & F_UPFOLD) && (t.family != FAM_RING || !(t.forms & F_CONV))) || (t.family == FAM_DIRECT) != (t.forms == F_CONV)) return false;
   for (int id : kAutoTiles) if (tile_index(id) < 0 || kTiles[tile_index(id)].family != FAM_REG) return false;
   return tile_index(kTileLnRing) >= 0 && tile_index(kTileLnPipe) >= 0;
 }
@@ -170,12 +186,12 @@ constexpr int gemm4_resident(const TileCfg& t) {
   return (t.wm * t.wn == 4 && 2 * ring <= 160 * 1024) ? 2 : 1;
 }
 
-struct Plan { int tile_idx; int split; int tiles_m, tiles_n; int k_per_split; int g_per_tile, chunks_per_split; bool unsupported; bool persist_ok; int band_rows, bands; bool persist3_ok; };
+struct Plan { int tile_idx; int split; int tiles_m, tiles_n; int k_per_split; int g_per_tile, chunks_per_split; bool unsupported; bool persist_ok; int band_rows, bands; bool persist3_ok; UpfoldTab upf; };
 
 // ---- launcher entry points of the family translation units: launch the kernel of tile pl.tile_idx in one form for
 // dtype DD_F16 / DD_BF16, or return DD_ERR_UNSUPPORTED where the tile's row holds no such instantiation
 using LaunchFn = int(int dtype, unsigned form, const GemmParams& p, const Plan& pl, hipStream_t s);
-__attribute__((visibility("hidden"))) LaunchFn launch_gemm1, launch_gemm2_dense, launch_gemm2_geglu, launch_gemm2_conv, launch_gemm3,
+__attribute__((visibility("hidden"))) LaunchFn launch_gemm1, launch_gemm2_dense, launch_gemm2_geglu, launch_gemm2_conv, launch_gemm2_upfold, launch_gemm3,
     launch_gemm4, launch_conv3s;
 
 // launch KERN; a kernel with more than 64 KB of dynamic LDS has its limit raised on each device's first launch

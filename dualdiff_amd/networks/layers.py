@@ -10,11 +10,13 @@ Activations travel as token-major 2-D tensors (m*h*w, c) plus the (m, h, w) trip
 only at the 4-channel latent boundary and when a caller hands in NCHW residuals.
 """
 import math
+import os
 
 import torch
 import torch.nn as nn
 
 from .. import ops as O
+from .. import upfold
 
 
 # ----------------------------------------------------------------------------- helpers ----
@@ -239,9 +241,40 @@ class Conv3x3(_Cached):
             self.__dict__["_pk_w"] = w.reshape(self.out_channels, 9 * self.cin_pad).contiguous()
         return self.__dict__["_pk_w"]
 
+    # Nearest upsample + conv: the three taps of an axis read at most two source pixels, so the tap slices that read the
+    # same pixel are summed ahead of time (fp32, rounded once) and the launch is a 2 x 2-tap conv with K = 4 Cin instead
+    # of 9 Cin (upfold.py; dd_gemm2u_kernel).  The layer folds only where the tracked table
+    # (tuned/gfx950_upfold.json) records the folded launch as measured faster than the 9-tap one for this very shape:
+    # many classes over few rows lose (each class streams its own weight matrix).  DD_UPFOLD=0 turns it off.
+    fold_upsample = os.environ.get("DD_UPFOLD", "1") != "0"
+
+    def folded_up(self, h, w, up_size, m=None):
+        """The weights folded for the nearest map (h, w) -> up_size, or None where the 9-tap form is kept: a map the fold
+        does not cover, or (m given: the model's path) a shape without a winning row in the tracked table."""
+        if not self.fold_upsample or up_size is None:
+            return None
+        size = (h, w, int(up_size[0]), int(up_size[1]))
+        if m is not None:
+            row = O.tuning.upfold_tuned(O.tuning.conv_upfold_key(m, h, w, self.cin_pad, self.out_channels, size[2], size[3],
+                                                                O._dtype_code(self.weight.dtype)))
+            if row is None or row[0] == 0:
+                return None
+        key = (self.weight.data_ptr(), self.weight._version) + size
+        cache = self.__dict__.setdefault("_pk_upfold", {})
+        hit = cache.get(size)
+        # (like _pk_wx: a first sight INSIDE a capture would record the fold's small torch kernels into the graph and redo
+        #  them on every replay; every caller warms up eagerly before it captures)
+        if hit is None or (hit[0] != key and not torch.cuda.is_current_stream_capturing()):
+            if not upfold.ok(*size, self.cin_pad, self.stride):
+                return None
+            with torch.no_grad():
+                hit = cache[size] = (key, upfold.fold_weight(self.packed, *size))
+        return hit[1]
+
     def run(self, x2d, m, h, w, up_size=None, **kw):
         """kw gn_next = (GroupNorm module, silu, want_x): see ops.conv3x3 (split-K reduce folded into that norm)."""
-        return O.conv3x3(x2d, self.packed, self.bias, m, h, w, stride=self.stride, up_size=up_size, **kw)
+        return O.conv3x3(x2d, self.packed, self.bias, m, h, w, stride=self.stride, up_size=up_size,
+                         upfold=self.folded_up(h, w, up_size, m), **kw)
 
     def out_hw(self, h, w, up_size=None):
         hv, wv = (h, w) if up_size is None else up_size

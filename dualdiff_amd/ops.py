@@ -13,7 +13,7 @@ import os as _os
 
 import torch
 
-from . import _native, _timer, _workspace, tuning
+from . import _native, _timer, _workspace, tuning, upfold as _upfold
 from ._native import DD_BF16, DD_EPI_GEGLU, DD_EPI_NONE, DD_EPI_SILU, DD_F16, AttnDesc, Gemm8Desc, GemmDesc, XAttnDesc
 from ._timer import KernelTimer, _stream, set_timer  # noqa: F401
 from ._workspace import workspace, workspace_owner  # noqa: F401
@@ -222,7 +222,8 @@ def thin_conv_ok(cin, cout, stride, m):
 
 
 def conv3x3(x, w, bias, m, hin, win, *, stride=1, up_size=None, rowvec=None, res=None,
-            alpha=1.0, out=None, accumulate=False, epilogue=DD_EPI_NONE, tile=0, split_k=0, gn_next=None, pad=1):
+            alpha=1.0, out=None, accumulate=False, epilogue=DD_EPI_NONE, tile=0, split_k=0, gn_next=None, pad=1,
+            upfold=None):
     """3x3 / pad 1 convolution as an implicit GEMM on an NHWC batch.
 
     pad=0 (stride 2, no upsample): diffusers' Downsample2D(padding=0) — F.pad(x, (0, 1, 0, 1)) then a 3x3 / stride 2 /
@@ -235,6 +236,9 @@ def conv3x3(x, w, bias, m, hin, win, *, stride=1, up_size=None, rowvec=None, res
 
     x: (m*hin*win, cin); w: (cout, 9*cin) packed [cout][ky][kx][cin]; optional nearest
     upsample of x to `up_size` first; rowvec: (m, cout) per-instance vector (time embedding).
+
+    upfold: the weights of `w` folded for this nearest map (upfold.fold_weight: (classes * cout, 4 * cin)); the launch is
+    then the 2 x 2-tap form dd_gemm2u_kernel with its own tuning key.  Without it a resize takes the 9-tap gather.
     Returns (m*hout*wout, cout)."""
     lib = _native.load()
     _need_gpu(x, w, bias, res, rowvec, out)
@@ -253,6 +257,13 @@ def conv3x3(x, w, bias, m, hin, win, *, stride=1, up_size=None, rowvec=None, res
     if w.shape[1] != 9 * cin or not w.is_contiguous():
         raise ValueError("conv weight must be contiguous [cout, 9*cin]")
     rows = m * hout * wout
+    if upfold is not None:
+        _need_gpu(upfold)
+        ncls = _upfold.num_classes(hin, win, hv, wv) if pad == 1 and stride == 1 and up_size is not None and cin % 64 == 0 else 0
+        if ncls == 0:
+            raise ValueError("conv3x3(upfold=...): no folded form for %dx%d -> %dx%d, stride %d, cin %d" % (hin, win, hv, wv, stride, cin))
+        if tuple(upfold.shape) != (ncls * cout, 4 * cin) or not upfold.is_contiguous() or upfold.dtype != x.dtype:
+            raise ValueError("folded conv weight must be contiguous %s [%d * cout, 4 * cin]" % (x.dtype, ncls))
     out = _out_or_new(out, (rows, cout), x.dtype, x.device, "conv3x3")
     if pad == 1 and thin_conv_ok(cin, cout, stride, m) and up_size is None and rowvec is None and res is None and alpha == 1.0 \
             and not accumulate and epilogue in (DD_EPI_NONE, DD_EPI_SILU) and tile == 0 and split_k == 0 \
@@ -271,12 +282,21 @@ def conv3x3(x, w, bias, m, hin, win, *, stride=1, up_size=None, rowvec=None, res
     d.conv = 1
     d.hin, d.win, d.cin, d.hv, d.wv = hin, win, cin, hv, wv
     d.hout, d.wout, d.stride = hout, wout, stride
+    if upfold is not None:
+        d.w, d.k, d.k1, d.upfold = upfold.data_ptr(), 4 * cin, 4 * cin, 1
     _epilogue_side(d, _dt(x), bias, rowvec, hout * wout, res, out, alpha, accumulate, epilogue, tile, split_k)
     L = tuning.launcher(lib, pad)
     what = "conv3x3" if pad == 1 else "conv3x3(pad=0)"
     if tile == 0 and split_k == 0:
         key = (tuning.conv_key if pad == 1 else tuning.conv_pad0_key)(m, hin, win, cin, cout, stride, hv, wv, d.dtype)
-        _tune(L, d, key, (rows, cout), x.dtype, x.device, (x, res))
+        hit = None
+        if upfold is not None:
+            key = tuning.conv_upfold_key(m, hin, win, cin, cout, hv, wv, d.dtype)
+            hit = tuning.upfold_tuned(key)
+        if hit is not None and hit[0] != 0:
+            d.tile, d.split_k = hit[:2]
+        else:
+            _tune(L, d, key, (rows, cout), x.dtype, x.device, (x, res))
     need = _workspace.attach(d, x.device, lambda: L.ws_bytes(d))
     if pad == 1 and gn_next is not None and GN_SPLITK and need > 0 and alpha == 1.0 and not accumulate \
             and epilogue == DD_EPI_NONE:

@@ -28,6 +28,10 @@ _COLD = os.environ.get("DD_AUTOTUNE_COLD", "1") != "0"
 # the ops module (bench.py assigns it there); ops hands it to tune() with every call.
 CHALLENGE_TILES = tuple(int(t) for t in os.environ.get("DD_TUNE_CHALLENGE", "").split(",") if t.strip())
 TUNE_TABLE_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuned", "gfx950.json")
+# The folded-upsample conv's own tracked table (conv_upfold_key -> tile, split-K): a row with tile 0 records a shape on which
+# the folded form was measured no faster than the 9-tap launch, which the layer then keeps (upfold_tuned).
+UPFOLD_TABLE_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuned", "gfx950_upfold.json")
+_UPFOLD = None
 _TUNED = {}
 _TABLE_LOADED = False
 _CHALLENGED = set()
@@ -55,6 +59,25 @@ def conv_key(m, hin, win, cin, cout, stride, hv, wv, dtype):
 def conv_pad0_key(m, hin, win, cin, cout, stride, hv, wv, dtype):
     """conv3x3(pad=0): its own entries, the pad-1 keys are untouched."""
     return conv_key(m, hin, win, cin, cout, stride, hv, wv, dtype) + ("p0",)
+
+
+def conv_upfold_key(m, hin, win, cin, cout, hv, wv, dtype):
+    """conv3x3(upfold=...): the folded-upsample form, its own entries beside the 9-tap key of the same layer."""
+    return conv_key(m, hin, win, cin, cout, 1, hv, wv, dtype) + ("uf",)
+
+
+def upfold_tuned(key):
+    """The tracked row (tile, split-K, 0) of a conv_upfold_key, or None; DD_TUNE_TABLE=0 ignores this table too."""
+    global _UPFOLD
+    if _UPFOLD is None:
+        _UPFOLD = {}
+        if os.environ.get("DD_TUNE_TABLE") != "0" and os.path.exists(UPFOLD_TABLE_PATH):
+            with open(UPFOLD_TABLE_PATH) as f:
+                blob = json.load(f)
+            if blob.get("arch") != "gfx950":
+                raise RuntimeError("tune cache %s is not for gfx950" % UPFOLD_TABLE_PATH)
+            _UPFOLD = {ast.literal_eval(k): _entry(v) for k, v in blob["entries"]}
+    return _UPFOLD.get(key)
 
 
 # ---- the table -----------------------------------------------------------------------------------------------------

@@ -166,6 +166,15 @@ typedef struct dd_gemm_desc {
   int64_t ld_ln_out;
   const void* lno_gamma;
   const void* lno_beta;
+  /* Folded nearest upsample (conv mode, stride 1, hv > hin, wv > win, both <= 64, cin % 64 == 0): under a nearest map the
+   * three taps of an axis read at most two distinct source pixels, so the tap slices of the weight that read the same pixel
+   * are summed ahead of time and every output pixel becomes a 2 x 2-tap conv with k = 4 * cin.  Per axis an output
+   * coordinate o with s = src(o) is of class 0 (taps read s-1 | s s: slot weights W-1 | W0+W1), 1 (s s | s+1: W-1+W0 | W1)
+   * or 2 (the last coordinate of an odd size, tap +1 outside the output: W-1 | W0); a pixel's class is 3 * (row class)
+   * + (column class).  `w` holds one [n][sy][sx][cin] matrix per NON-EMPTY class, in class order; k = 4 * cin.  A map
+   * with a coordinate that fits no class (three distinct sources, a downscale) is DD_ERR_UNSUPPORTED: the caller keeps
+   * the 9-tap form (upfold = 0).  Only LDS-DMA ring tiles carry the kernel (dd_gemm2u_kernel). */
+  int32_t upfold;
 } dd_gemm_desc;
 
 int dd_gemm(const dd_gemm_desc* d, dd_stream_t stream);

@@ -5,7 +5,7 @@ set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 L=$R/dualdiff_amd/lib
 python3 -c "import sys; sys.path.insert(0, '$R'); from dualdiff_amd import _build; _build.build_native()"
-GEMM="gemm1 gemm23 gemm2_geglu gemm2_conv gemm4 conv3s"      # the GEMM / conv kernel families' translation units
+GEMM="gemm1 gemm23 gemm2_geglu gemm2_conv gemm2_upfold gemm4 conv3s"      # the GEMM / conv kernel families' translation units
 for V in NOMFMA NODMA; do
   v=$(echo $V | tr A-Z a-z)
   for S in $GEMM; do
