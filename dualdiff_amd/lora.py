@@ -104,11 +104,12 @@ def fold_lora_(model, lora_state_dict, scale=1.0, network_alphas=None):
         for attn, lin, down, up, factor in plan:
             delta = factor * (up.to(lin.weight.device, torch.float32) @ down.to(lin.weight.device, torch.float32))
             w = lin.weight.detach().float().reshape(lin.out_features, -1) + delta
-            lin.weight.copy_(w.reshape(lin.weight.shape).to(lin.weight.dtype))    # bumps _version: folded products refresh
+            lin.weight.copy_(w.reshape(lin.weight.shape).to(lin.weight.dtype))    # bumps _version: every derived weight follows
+            # (layers.derived); the drops and _invalidate below are what ends the forward graphs recorded with the old weights
             lin._drop_cache()
             attn._drop_cache()
             n += 1
-    for mod in model.modules():        # folded connector / proj_out products are keyed on parameter versions
+    for mod in model.modules():
         if hasattr(mod, "_invalidate"):
             mod._invalidate()
     return n

@@ -92,25 +92,22 @@ class BasicMultiviewTransformerBlock(BasicTransformerBlock):
     def _folded_out(self, nb):
         """(W, b) of `connector(sum of nb to_out applications)` as ONE Linear on the summed attention outputs:
         zero_linear: W = Wc Wo, b = Wc (nb b_o) + b_c; gated: W = diag(tanh a) Wo, b = tanh(a) * nb b_o;
-        none: W = Wo, b = nb b_o.  Folded in fp32 whenever a parameter changes."""
+        none: W = Wo, b = nb b_o.  Folded in fp32 (layers.derived, kept on attn4.to_out[0])."""
         wo, bo = self.attn4.to_out[0].weight, self.attn4.to_out[0].bias
         cp = [] if self.connector is None else list(self.connector.parameters())
-        key = (nb, wo._version, bo._version, wo.data_ptr()) + tuple((t._version, t.data_ptr()) for t in cp)
-        holder = self.attn4.to_out[0].__dict__
-        hit = holder.get("_pk_fold")
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                wof, bof = wo.detach().float(), bo.detach().float() * nb
-                if self.zero_module_type == "zero_linear":
-                    wc, bc = self.connector.weight.detach().float(), self.connector.bias.detach().float()
-                    w, b = wc @ wof, wc @ bof + bc
-                elif self.zero_module_type == "gated":
-                    g = torch.tanh(self.connector.alpha.detach().float())
-                    w, b = g[:, None] * wof, g * bof
-                else:
-                    w, b = wof, bof
-                hit = holder["_pk_fold"] = (key, w.to(wo.dtype).contiguous(), b.to(wo.dtype).contiguous())
-        return hit[1], hit[2]
+
+        def build():
+            wof, bof = wo.detach().float(), bo.detach().float() * nb
+            if self.zero_module_type == "zero_linear":
+                wc, bc = self.connector.weight.detach().float(), self.connector.bias.detach().float()
+                w, b = wc @ wof, wc @ bof + bc
+            elif self.zero_module_type == "gated":
+                g = torch.tanh(self.connector.alpha.detach().float())
+                w, b = g[:, None] * wof, g * bof
+            else:
+                w, b = wof, bof
+            return w.to(wo.dtype).contiguous(), b.to(wo.dtype).contiguous()
+        return layers.derived(self.attn4.to_out[0], "fold", [wo, bo] + cp, build, slot=nb)
 
     @property
     def n_cam(self):

@@ -11,7 +11,7 @@ import os
 import torch
 
 from .. import ops as O
-from .layers import HIPAttnProcessor, Linear
+from .layers import HIPAttnProcessor, Linear, _Cached, derived
 
 SPLIT_SIZE = int(os.getenv("SPLIT_SIZE", -1))
 
@@ -41,7 +41,7 @@ class XFormersAttnProcessor(HIPAttnProcessor):
         return HIPAttnProcessor.__call__(self, attn, hidden_states, encoder_hidden_states, attention_mask, temb, **kw)
 
 
-class Adapter_XFormersAttnProcessor(torch.nn.Module):
+class Adapter_XFormersAttnProcessor(_Cached):
     """Box / class adapter on a text cross-attention (box_adapter.py:177-411), on the HIP kernels.
 
     The context is [cam + text | box tokens | class tokens] (`num_tokens` each for the last two,
@@ -64,21 +64,8 @@ class Adapter_XFormersAttnProcessor(torch.nn.Module):
         self.to_v_cls = Linear(d, hidden_size, bias=False)
 
     def _fused(self, a, b):
-        key = "_pk_" + a + b
-        if key not in self.__dict__:
-            self.__dict__[key] = torch.cat([getattr(self, a).weight.detach(), getattr(self, b).weight.detach()],
-                                           dim=0).contiguous()
-        return self.__dict__[key]
-
-    def _apply(self, fn, *a, **k):
-        for key in [k_ for k_ in self.__dict__ if k_.startswith("_pk_")]:
-            del self.__dict__[key]
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        for key in [k_ for k_ in self.__dict__ if k_.startswith("_pk_")]:
-            del self.__dict__[key]
-        return super()._load_from_state_dict(*a, **k)
+        ws = [getattr(self, a).weight, getattr(self, b).weight]
+        return derived(self, a + b, ws, lambda: torch.cat([w.detach() for w in ws], dim=0).contiguous())
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, **kw):
         n = hidden_states.shape[0]

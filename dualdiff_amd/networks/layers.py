@@ -27,7 +27,7 @@ CACHE_EPOCH = [0]
 
 
 class _Cached(nn.Module):
-    """Module with lazily packed kernel-layout weights; caches drop on .to()/load_state_dict."""
+    """Module with lazily derived kernel-layout weights (`derived`); its entries drop on .to()/load_state_dict."""
 
     def _drop_cache(self):
         CACHE_EPOCH[0] += 1
@@ -41,6 +41,40 @@ class _Cached(nn.Module):
     def _load_from_state_dict(self, *a, **k):
         self._drop_cache()
         return super()._load_from_state_dict(*a, **k)
+
+
+def _weight(mod, name=None):
+    """mod.weight, or mod.<name>.weight: the parameter itself, not through nn.Module.__getattr__ (1 us a look, and the
+    eager forward asks several hundred times)."""
+    return (mod if name is None else mod._modules[name])._parameters["weight"]
+
+
+def _capturing():
+    try:
+        return torch.cuda.is_current_stream_capturing()
+    except RuntimeError:               # a build of torch with GPU support on a machine without one (CPU modules)
+        return False
+
+
+def derived(holder, name, params, build, slot=None):
+    """holder.__dict__["_pk_" + name] (per `slot` where one name holds several entries): the value build() returns,
+    cached against the address and version of every tensor in `params` (None entries allowed).  THE rule for every
+    kernel-layout copy of a parameter: an in-place update or a new storage rebuilds it at the next eager call; inside a
+    stream capture a stale entry is kept as it is (every caller warms up eagerly before it captures: a rebuild would
+    record the packing kernels into the graph and redo them on every replay) and only a missing one is built.
+    `_Cached._drop_cache` of the holder forgets it.  Recorded graphs do not follow: see CACHE_EPOCH."""
+    try:
+        key = [t if t is None else (t.data_ptr(), t._version) for t in params]
+    except RuntimeError:               # inference tensors do not count versions
+        key = [t if t is None else (t.data_ptr(), 0 if t.is_inference() else t._version) for t in params]
+    entries, k = holder.__dict__, "_pk_" + name
+    if slot is not None:
+        entries, k = entries.setdefault(k, {}), slot
+    hit = entries.get(k)
+    if hit is None or (hit[0] != key and not _capturing()):
+        with torch.no_grad():
+            hit = entries[k] = (key, build())
+    return hit[1]
 
 
 # ---- context length in device memory (round 6) ----------------------------------------------------------------
@@ -151,31 +185,22 @@ class Linear(_Cached):
 
     @property
     def w2d(self):
-        if "_pk_w" not in self.__dict__:
-            self.__dict__["_pk_w"] = _pad_cols(self.weight.detach().reshape(self.out_features, -1))
-        return self.__dict__["_pk_w"]
+        """(out, K padded to a multiple of 8); a view of the live parameter where nothing is padded."""
+        w = _weight(self)
+        return derived(self, "w", [w], lambda: _pad_cols(w.detach().reshape(self.out_features, -1)))
 
     @property
     def wx(self):
         """The (320, 320) weight in the layout dd_xattn320 streams (ops.xattn_pack_weight), packed lazily like w2d and
         owned by this module."""
-        # w2d of a 320 x 320 layer ALIASES the live parameter, so an in-place update (optimizer step, weight.mul_) is seen
-        # by the three-launch path at once; the packed copy follows through the parameter's version counter (re-packed
-        # outside a capture only: a graph that recorded the old buffer keeps it alive and consistent with itself)
-        ver = (self.weight.data_ptr(), self.weight._version)
-        hit = self.__dict__.get("_pk_wx")
-        if hit is None or (hit[1] != ver and not torch.cuda.is_current_stream_capturing()):
-            hit = self.__dict__["_pk_wx"] = (O.xattn_pack_weight(self.w2d), ver)
-        return hit[0]
+        return derived(self, "wx", [_weight(self)], lambda: O.xattn_pack_weight(self.w2d))
 
     fp8_mfma = False   # extension (BASELINE configs[4]): W8A8 on the fp8 matrix path (dd_gemm8) where it pays: K >= 640, wide output
 
     @property
     def w8p(self):
         """(float8_e4m3fn [n, K padded to 128], fp32 scale [n]): the W8 operand of ops.gemm8, packed lazily."""
-        if "_pk_w8p" not in self.__dict__:
-            self.__dict__["_pk_w8p"] = O.quantize_fp8_padded(self.w2d)
-        return self.__dict__["_pk_w8p"]
+        return derived(self, "w8p", [_weight(self)], lambda: O.quantize_fp8_padded(self.w2d))
 
     def run(self, x2d, ln_next=None, **kw):
         """x2d: (rows, K) — fused-epilogue GEMM (see ops.gemm kwargs).  ln_next: the LayerNorm module that will
@@ -202,7 +227,7 @@ class Linear(_Cached):
             return O.gemm8(a8, sa, w8, sw, self.bias, dtype=x2d.dtype, geglu=kw.get("epilogue") == O.DD_EPI_GEGLU)
         if not ln_fold_ok(norm, self.in_features, self.out_features, x2d):
             return self.run(norm.run(x2d), **kw)
-        w, ln = fold_layernorm(self.__dict__, "_pk_ln", norm, [self.weight], [self.bias])
+        w, ln = fold_layernorm(self, "ln", norm, [self.weight], [self.bias])
         return O.gemm(x2d, w, None, ln=ln, **kw)
 
     def forward(self, x):
@@ -232,14 +257,14 @@ class Conv3x3(_Cached):
 
     @property
     def packed(self):
-        if "_pk_w" not in self.__dict__:
-            w = self.weight.detach().permute(0, 2, 3, 1)              # [cout, 3, 3, cin]
+        def build():
+            w = _weight(self).detach().permute(0, 2, 3, 1)            # [cout, 3, 3, cin]
             if self.cin_pad != self.in_channels:
                 wp = w.new_zeros((self.out_channels, 3, 3, self.cin_pad))
                 wp[..., :self.in_channels] = w
                 w = wp
-            self.__dict__["_pk_w"] = w.reshape(self.out_channels, 9 * self.cin_pad).contiguous()
-        return self.__dict__["_pk_w"]
+            return w.reshape(self.out_channels, 9 * self.cin_pad).contiguous()
+        return derived(self, "w", [_weight(self)], build)
 
     # Nearest upsample + conv: the three taps of an axis read at most two source pixels, so the tap slices that read the
     # same pixel are summed ahead of time (fp32, rounded once) and the launch is a 2 x 2-tap conv with K = 4 Cin instead
@@ -259,17 +284,9 @@ class Conv3x3(_Cached):
                                                                 O._dtype_code(self.weight.dtype)))
             if row is None or row[0] == 0:
                 return None
-        key = (self.weight.data_ptr(), self.weight._version) + size
-        cache = self.__dict__.setdefault("_pk_upfold", {})
-        hit = cache.get(size)
-        # (like _pk_wx: a first sight INSIDE a capture would record the fold's small torch kernels into the graph and redo
-        #  them on every replay; every caller warms up eagerly before it captures)
-        if hit is None or (hit[0] != key and not torch.cuda.is_current_stream_capturing()):
-            if not upfold.ok(*size, self.cin_pad, self.stride):
-                return None
-            with torch.no_grad():
-                hit = cache[size] = (key, upfold.fold_weight(self.packed, *size))
-        return hit[1]
+        if not upfold.ok(*size, self.cin_pad, self.stride):
+            return None
+        return derived(self, "upfold", [_weight(self)], lambda: upfold.fold_weight(self.packed, *size), slot=size)
 
     def run(self, x2d, m, h, w, up_size=None, **kw):
         """kw gn_next = (GroupNorm module, silu, want_x): see ops.conv3x3 (split-K reduce folded into that norm)."""
@@ -392,25 +409,20 @@ XATTN_FUSED = __import__("os").environ.get("DD_XATTN_FUSED", "1") != "0"
 HEAD_MAJOR = __import__("os").environ.get("DD_ATTN_HEAD_MAJOR", "1") != "0"
 
 
-def fold_layernorm(cache, key, norm, weights, biases):
+def fold_layernorm(holder, name, norm, weights, biases):
     """LayerNorm(x) @ W^T + b  ==  rstd * (x @ W'^T - mean * colsum) + b'   with
     W' = W * gamma, colsum[n] = sum_k W'[n,k] (of the ROUNDED W', the matrix the kernel multiplies by),
     b' = W beta + b.  `weights` / `biases`: lists concatenated along N (fused projections).
-    Cached in `cache[key]` until any involved parameter changes.  Returns (W', (colsum, b', eps))."""
-    params = [norm.weight, norm.bias] + list(weights) + [b for b in biases if b is not None]
-    ver = tuple((t._version, t.data_ptr()) for t in params)
-    hit = cache.get(key)
-    if hit is not None and hit[0] == ver:
-        return hit[1], hit[2]
-    with torch.no_grad():
+    A `derived` entry `name` of `holder`.  Returns (W', (colsum, b', eps))."""
+    def build():
         w = torch.cat([t.detach().reshape(t.shape[0], -1) for t in weights], dim=0).float()
         b = torch.cat([(bb.detach().float() if bb is not None else torch.zeros(t.shape[0], device=t.device))
                        for t, bb in zip(weights, biases)])
         wp = (w * norm.weight.detach().float()[None, :]).to(weights[0].dtype).contiguous()
         colsum = wp.float().sum(dim=1).contiguous()
         lnb = (w @ norm.bias.detach().float() + b).contiguous()
-    cache[key] = (ver, wp, (colsum, lnb, norm.eps))
-    return wp, (colsum, lnb, norm.eps)
+        return wp, (colsum, lnb, norm.eps)
+    return derived(holder, name, [norm.weight, norm.bias] + list(weights) + list(biases), build)
 
 
 class _Dropout(nn.Module):
@@ -561,23 +573,24 @@ class Attention(_Cached):
 
     # fused weights ------------------------------------------------------------------------
     def _fused(self, names):
-        key = "_pk_" + "".join(names)
-        if key not in self.__dict__:
-            self.__dict__[key] = torch.cat([getattr(self, n).weight.detach() for n in names], dim=0).contiguous()
-        return self.__dict__[key]
+        ws = [_weight(self, n) for n in names]
+        return derived(self, "".join(names), ws, lambda: torch.cat([w.detach() for w in ws], dim=0).contiguous())
 
     def _fused_bias(self, names):
         """Concatenated biases of the fused projection (None for the bias-free SD layers)."""
         mods = [getattr(self, n) for n in names]
         if all(m.bias is None for m in mods):
             return None
-        key = "_pk_b_" + "".join(names)
-        if key not in self.__dict__:
-            self.__dict__[key] = torch.cat([
-                m.bias.detach() if m.bias is not None else m.weight.new_zeros(m.out_features) for m in mods]).contiguous()
-        return self.__dict__[key]
+        return derived(self, "b_" + "".join(names), [m.bias for m in mods], lambda: torch.cat([
+            m.bias.detach() if m.bias is not None else m.weight.new_zeros(m.out_features) for m in mods]).contiguous())
 
     fp8_mfma = False   # extension: fused Q|K|V projection as W8A8 on the fp8 matrix path (enable_fp8_weights)
+
+    def _w8p_qkv(self):
+        """The fused Q|K|V matrix as the W8 operand of ops.gemm8 (Linear.w8p)."""
+        names = ("to_q", "to_k", "to_v")
+        return derived(self, "w8p_qkv", [_weight(self, n) for n in names],
+                       lambda: O.quantize_fp8_padded(self._fused(names)))
 
     def _hm(self, planes):
         """head_major argument of the projection GEMMs: [rows][D] planes per head, the Q planes carrying
@@ -591,10 +604,7 @@ class Attention(_Cached):
         hm = self._hm(self.heads) if head_major else None
         names = ("to_q", "to_k", "to_v")
         if self.fp8_mfma and norm is not None and fp8_mfma_ok(norm, x2d.shape[1], 3 * self.inner_dim, x2d):
-            key = "_pk_w8p_qkv"
-            if key not in self.__dict__:
-                self.__dict__[key] = O.quantize_fp8_padded(self._fused(names))
-            w8, sw = self.__dict__[key]
+            w8, sw = self._w8p_qkv()
             a8, sa = O.rowquant_fp8(x2d, (norm.weight, norm.bias, norm.eps))
             return O.gemm8(a8, sa, w8, sw, self._fused_bias(names), head_major=hm, dtype=x2d.dtype)
         if norm is not None:
@@ -602,7 +612,7 @@ class Attention(_Cached):
                 return O.gemm(norm.run(x2d), self._fused(("to_q", "to_k", "to_v")),
                               self._fused_bias(("to_q", "to_k", "to_v")), head_major=hm)
             mods = (self.to_q, self.to_k, self.to_v)
-            w, ln = fold_layernorm(self.__dict__, "_pk_ln_qkv", norm, [m.weight for m in mods], [m.bias for m in mods])
+            w, ln = fold_layernorm(self, "ln_qkv", norm, [m.weight for m in mods], [m.bias for m in mods])
             return O.gemm(x2d, w, None, ln=ln, head_major=hm)
         return O.gemm(x2d, self._fused(("to_q", "to_k", "to_v")), self._fused_bias(("to_q", "to_k", "to_v")),
                       head_major=hm)
@@ -790,15 +800,12 @@ class Transformer2DModel(nn.Module):
     def _folded_ff_out(self, blk):
         w2, b2 = blk.ff.net[2].weight, blk.ff.net[2].bias
         wp, bp = self.proj_out.weight, self.proj_out.bias
-        key = (w2._version, b2._version, wp._version, bp._version, w2.data_ptr(), wp.data_ptr())
-        hit = self.proj_out.__dict__.get("_pk_fold")
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                wpf = wp.detach().float().reshape(wp.shape[0], -1)
-                w = torch.cat([wpf @ w2.detach().float(), wpf], dim=1).to(wp.dtype).contiguous()
-                b = (wpf @ b2.detach().float() + bp.detach().float()).to(wp.dtype).contiguous()
-            hit = self.proj_out.__dict__["_pk_fold"] = (key, w, b)
-        return hit[1], hit[2]
+
+        def build():
+            wpf = wp.detach().float().reshape(wp.shape[0], -1)
+            w = torch.cat([wpf @ w2.detach().float(), wpf], dim=1).to(wp.dtype).contiguous()
+            return w, (wpf @ b2.detach().float() + bp.detach().float()).to(wp.dtype).contiguous()
+        return derived(self.proj_out, "fold", [w2, b2, wp, bp], build)
 
     def run(self, x, m, h, w, ctx2d, lc):
         a = self.norm.run(x, m, h * w, False)
@@ -934,16 +941,16 @@ class TimeEmbProjBank:
 
     def __init__(self, model):
         self.resnets = [mod for mod in model.modules() if isinstance(mod, ResnetBlock2D)]
-        self._w = self._b = None
 
-    def invalidate(self):
-        self._w = self._b = None
+    def stacked(self):
+        """(weights, biases) of every time_emb_proj stacked along N."""
+        ps = [r._modules["time_emb_proj"]._parameters for r in self.resnets]        # (see _weight)
+        ws, bs = [p["weight"] for p in ps], [p["bias"] for p in ps]
+        return derived(self, "wb", ws + bs, lambda: (torch.cat([w.detach() for w in ws], 0).contiguous(),
+                                                     torch.cat([b.detach() for b in bs], 0).contiguous()))
 
     def run(self, emb_act):
-        if self._w is None or self._w.dtype != emb_act.dtype or self._w.device != emb_act.device:
-            self._w = torch.cat([r.time_emb_proj.weight.detach() for r in self.resnets], 0).contiguous()
-            self._b = torch.cat([r.time_emb_proj.bias.detach() for r in self.resnets], 0).contiguous()
-        allv = O.gemm(emb_act, self._w, self._b)
+        allv = O.gemm(emb_act, *self.stacked())
         out, off = {}, 0
         for r in self.resnets:
             out[id(r)] = allv[:, off:off + r.out_channels]
@@ -964,19 +971,22 @@ class CrossKVBank:
             mod = getattr(blk, "attn2", None) if isinstance(blk, BasicTransformerBlock) else None
             if mod is not None and mod.is_cross:
                 self.layers.append(mod)
-        self._w = None
-        self._key = None
+
+    def banked(self, k):
+        """The layers whose K/V projection of a `k`-wide context goes through the bank."""
+        return [m for m in self.layers if isinstance(m.processor, HIPAttnProcessor)
+                and m.to_k.in_features == k and m.to_k.bias is None and m.to_v.bias is None]
+
+    def stacked(self, mods):
+        """The fused K|V matrices of `mods` stacked along N."""
+        return derived(self, "kv", [_weight(m, n) for m in mods for n in ("to_k", "to_v")],
+                       lambda: torch.cat([m._fused(("to_k", "to_v")) for m in mods], dim=0).contiguous())
 
     def run(self, ctx2d):
-        mods = [m for m in self.layers if isinstance(m.processor, HIPAttnProcessor)
-                and m.to_k.in_features == ctx2d.shape[1] and m.to_k.bias is None and m.to_v.bias is None]
+        mods = self.banked(ctx2d.shape[1])
         if not mods:
             return
-        key = tuple((m.to_k.weight._version, m.to_v.weight._version, m.to_k.weight.data_ptr()) for m in mods)
-        if self._w is None or self._key != key or self._w.dtype != ctx2d.dtype or self._w.device != ctx2d.device:
-            self._w = torch.cat([m._fused(("to_k", "to_v")) for m in mods], dim=0).contiguous()
-            self._key = key
-        allkv = O.gemm(ctx2d, self._w)
+        allkv = O.gemm(ctx2d, self.stacked(mods))
         off = 0
         for m in mods:
             n2 = 2 * m.inner_dim

@@ -333,8 +333,7 @@ class ModelBase(nn.Module):
         return self.__dict__["_temb_bank"]
 
     def _invalidate(self):
-        if self.__dict__.get("_temb_bank") is not None:
-            self.__dict__["_temb_bank"].invalidate()
+        self.__dict__["_temb_bank"] = self.__dict__["_kv_bank"] = None         # with their stacked matrices
         if self.__dict__.get("_fwd_graphs") is not None:
             self.__dict__["_fwd_graphs"].clear()
 

@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops as O
-from .layers import LayerNorm, Linear, _Cached
+from .layers import LayerNorm, Linear, _Cached, derived
 
 QUICK_GELU = 1.702
 MAX_TOKENS = 77
@@ -60,11 +60,10 @@ class CLIPAttention(_Cached):
         self.out_proj = Linear(hidden_size, hidden_size)
 
     def _fused(self):
-        if "_pk_qkv" not in self.__dict__:
-            self.__dict__["_pk_qkv"] = (
-                torch.cat([getattr(self, n).weight.detach() for n in self.NAMES], dim=0).contiguous(),
-                torch.cat([getattr(self, n).bias.detach() for n in self.NAMES]).contiguous())
-        return self.__dict__["_pk_qkv"]
+        ps = [getattr(self, n) for n in self.NAMES]
+        return derived(self, "qkv", [p.weight for p in ps] + [p.bias for p in ps], lambda: (
+            torch.cat([p.weight.detach() for p in ps], dim=0).contiguous(),
+            torch.cat([p.bias.detach() for p in ps]).contiguous()))
 
     def run(self, h, res, batch, l):
         c = self.heads * self.head_dim
@@ -82,10 +81,8 @@ class CLIPMLP(_Cached):
 
     def _bias2(self):
         """fc2's bias times 1.702 (fp32 product, one rounding): what alpha = 1 / 1.702 turns back into the bias."""
-        if "_pk_b2" not in self.__dict__:
-            b = self.fc2.bias.detach()
-            self.__dict__["_pk_b2"] = (b.float() * QUICK_GELU).to(b.dtype).contiguous()
-        return self.__dict__["_pk_b2"]
+        b = self.fc2.bias
+        return derived(self, "b2", [b], lambda: (b.detach().float() * QUICK_GELU).to(b.dtype).contiguous())
 
     def run(self, h, res):
         g = self.fc1.run(h, alpha=QUICK_GELU, epilogue=O.DD_EPI_SILU)          # 1.702 * quick_gelu(fc1(h))

@@ -12,10 +12,10 @@ import torch
 import torch.nn as nn
 
 from .. import ops as O
-from .layers import Linear, _Dropout, as_nchw_view, to_nhwc
+from .layers import Linear, _Cached, _Dropout, as_nchw_view, derived, to_nhwc
 
 
-class _SFABase(nn.Module):
+class _SFABase(_Cached):
     heads = 8
 
     def _io(self, hidden_states, encoder_hidden_states):
@@ -48,31 +48,25 @@ class txt_con_XFormersAttn(_SFABase):
         self.rescale_output_factor = 1.0
         self.residual_connection = True
 
+    def _fused(self):
+        ws = [self.to_k.weight, self.to_v.weight]
+        return derived(self, "kv", ws, lambda: torch.cat([w.detach() for w in ws], 0).contiguous())
+
     def run(self, x, b, lq, e2d, lk):
         c = self.inner_dim
-        if "_pk_kv" not in self.__dict__ or self.__dict__["_pk_kv"].dtype != x.dtype \
-                or self.__dict__["_pk_kv"].device != x.device:
-            self.__dict__["_pk_kv"] = torch.cat([self.to_k.weight.detach(), self.to_v.weight.detach()], 0).contiguous()
+        wkv = self._fused()
         from . import layers
         if layers.XATTN_FUSED and O.xattn320_ok(c, self.heads, lk, x.shape[0]) and x.shape[1] == c:
             # to_q -> attention over the text keys -> to_out + bias + residual in ONE launch (csrc/xattn.hip); K | V of
             # the text tokens as one contiguous [keys][40] block per head (the form the kernel streams fastest)
             hd = self.heads
-            kvh = O.gemm(e2d, self.__dict__["_pk_kv"], head_major=(c // hd, 0, 1.0))        # (16, b * lk, 40)
+            kvh = O.gemm(e2d, wkv, head_major=(c // hd, 0, 1.0))        # (16, b * lk, 40)
             return O.xattn320(x, self.to_q.wx, self.to_out[0].wx, self.to_out[0].bias, kvh[:hd], kvh[hd:], b, lq, lk,
                               self.scale, res=x if self.residual_connection else None)
-        kv = O.gemm(e2d, self.__dict__["_pk_kv"])
+        kv = O.gemm(e2d, wkv)
         q = self.to_q.run(x)
         o = O.attention(q, kv[:, :c], kv[:, c:], b, lq, lk, self.heads, c // self.heads, self.scale)
         return self.to_out[0].run(o, res=x if self.residual_connection else None)
-
-    def _apply(self, fn, *a, **k):
-        self.__dict__.pop("_pk_kv", None)
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self.__dict__.pop("_pk_kv", None)
-        return super()._load_from_state_dict(*a, **k)
 
     def forward(self, attn=None, hidden_states=None, encoder_hidden_states=None, attention_mask=None, temb=None):
         assert attention_mask is None and temb is None

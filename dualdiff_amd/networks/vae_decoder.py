@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops as O
-from .layers import Conv3x3, GroupNorm, Linear, Upsample2D, _Cached, _Dropout, to_nhwc
+from .layers import Conv3x3, GroupNorm, Linear, Upsample2D, _Cached, _Dropout, derived, to_nhwc
 
 SCALING_FACTOR = 0.18215
 
@@ -55,10 +55,9 @@ class VaeAttention(_Cached):
         self.scale = channels ** -0.5
 
     def _qk(self):
-        if "_pk_qk" not in self.__dict__:
-            self.__dict__["_pk_qk"] = (torch.cat([self.to_q.weight, self.to_k.weight]).detach().contiguous(),
-                                       torch.cat([self.to_q.bias, self.to_k.bias]).detach().contiguous())
-        return self.__dict__["_pk_qk"]
+        q, k = self.to_q, self.to_k
+        return derived(self, "qk", [q.weight, k.weight, q.bias, k.bias], lambda: (
+            torch.cat([q.weight, k.weight]).detach().contiguous(), torch.cat([q.bias, k.bias]).detach().contiguous()))
 
     def run(self, x, m, hw):
         c = self.channels
@@ -133,15 +132,16 @@ class AutoencoderKLDecoder(nn.Module):
 
     def _pq(self):
         """post_quant_conv packed for the 8-channel padded latent layout: (8, 8), zero padding."""
-        d = self.post_quant_conv.__dict__
-        if "_pk_pq" not in d:
-            w = self.post_quant_conv.weight.detach().reshape(4, 4)
+        pq = self.post_quant_conv
+
+        def build():
+            w = pq.weight.detach().reshape(4, 4)
             wp = w.new_zeros((8, 8))
             wp[:4, :4] = w
             bp = w.new_zeros((8,))
-            bp[:4] = self.post_quant_conv.bias.detach()
-            d["_pk_pq"] = (wp.contiguous(), bp.contiguous())
-        return d["_pk_pq"]
+            bp[:4] = pq.bias.detach()
+            return wp.contiguous(), bp.contiguous()
+        return derived(pq, "pq", [pq.weight, pq.bias], build)
 
     @torch.no_grad()
     def decode(self, z, pre_scale=1.0):

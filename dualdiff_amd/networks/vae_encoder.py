@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops as O
-from .layers import Conv3x3, GroupNorm, Linear
+from .layers import Conv3x3, GroupNorm, Linear, derived
 from .vae_decoder import SCALING_FACTOR, VaeMidBlock, VaeResnetBlock2D
 
 
@@ -125,11 +125,9 @@ class AutoencoderKLEncoder(nn.Module):
 
     def _q(self):
         """quant_conv as the posterior kernel reads it: fp32 (8, 8) weight and (8,) bias."""
-        d = self.quant_conv.__dict__
-        if "_pk_q32" not in d:
-            d["_pk_q32"] = (self.quant_conv.weight.detach().reshape(8, 8).float().contiguous(),
-                            self.quant_conv.bias.detach().float().contiguous())
-        return d["_pk_q32"]
+        q = self.quant_conv
+        return derived(q, "q32", [q.weight, q.bias], lambda: (q.weight.detach().reshape(8, 8).float().contiguous(),
+                                                              q.bias.detach().float().contiguous()))
 
     @torch.no_grad()
     def encode(self, x):
