@@ -510,6 +510,56 @@ def image_load_u8(frames, size, box=None, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0
     return out
 
 
+def jpeg_encode_u8(frames, quality=75, out=None, capacity=None):
+    """uint8 frames (m, H, W, 3) -> the files PIL's `Image.save(name.jpg, quality=quality)` writes, byte for byte
+    (dd_jpeg_encode_u8): baseline, 4:2:0 chroma, the standard Huffman tables.  -> (buf (m, capacity) uint8, lengths (m,)
+    int32), both on the device: file i is buf[i, :lengths[i]].  capacity defaults to header + H * W bytes per frame (at least the header and the end marker); a
+    length above the capacity is the file's true length, the row then holds its first `capacity` bytes.  Nothing is read
+    back.  The header and the tables are built on the host once per (H, W, quality) and kept per device
+    (pipeline.image_output.device_jpeg_tables), the scratch buffer is ops.workspace's: call once, on the capture stream or
+    under the same workspace_owner, before capturing the launches in a graph."""
+    what = "jpeg_encode_u8"
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
+        raise ValueError("%s takes an (m, H, W, 3) frame batch, got %s" % (what, tuple(frames.shape)))
+    if frames.dtype != torch.uint8:
+        raise ValueError("%s takes uint8 frames, got %s" % (what, frames.dtype))
+    if not frames.is_contiguous():
+        raise ValueError("%s takes a contiguous NHWC tensor" % what)
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError("quality must be an int in 1..100, got %r" % (quality,))
+    m, h, w = frames.shape[0], frames.shape[1], frames.shape[2]
+    if h > 65535 or w > 65535:
+        raise ValueError("%s: a JPEG frame is at most 65535 x 65535, got %d x %d" % (what, h, w))
+    from .pipeline.image_output import device_jpeg_tables, jpeg_header
+    header_len = len(jpeg_header(h, w, quality))
+    if out is not None:
+        if out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != m or not out.is_contiguous():
+            raise ValueError("%s: out must be a contiguous uint8 (%d, capacity) tensor" % (what, m))
+        if capacity is not None and int(capacity) != out.shape[1]:
+            raise ValueError("%s: capacity %r does not match out %s" % (what, capacity, tuple(out.shape)))
+        capacity = out.shape[1]
+    capacity = header_len + max(h * w, 2) if capacity is None else int(capacity)        # 1 x 1: room for the end marker
+    if capacity < header_len + 2:
+        raise ValueError("%s: capacity must be at least the header and the end marker (%d bytes), got %d"
+                         % (what, header_len + 2, capacity))
+    _need_gpu(frames, out)
+    if out is None:
+        out = torch.empty((m, capacity), dtype=torch.uint8, device=frames.device)
+    lengths = torch.empty((m,), dtype=torch.int32, device=frames.device)
+    lib = _native.load()
+    need = lib.dd_jpeg_workspace_bytes(m, h, w)
+    if need < 0:
+        raise _native.Unsupported("dualdiff_amd.%s: %d frames of %d x %d are more than one call takes" % (what, m, h, w))
+    header, tables = device_jpeg_tables(h, w, quality, frames.device)
+    ws = workspace(need, frames.device, kind="jpeg")
+    _timer.launch(what, lib.dd_jpeg_encode_u8, _ptr(frames), m, h, w, _ptr(header), header_len, _ptr(tables), _ptr(ws),
+                  ws.numel() * 4, _ptr(out), capacity, _ptr(lengths), _stream(),
+                  # frames read, the int16 coefficients (768 bytes per MCU) written once and read twice; the bit stream is as
+                  # long as the content makes it and is not booked
+                  book=lambda: ("dd_jpeg_encode", 0.0, float(frames.numel() + 3 * 768 * m * ((h + 15) // 16) * ((w + 15) // 16))))
+    return out, lengths
+
+
 BOX_POINT_MODES = {"all-xyz": 0, "cxyz": 1}      # dataset/utils.py:222-226; points per box 8 / 4
 BOX_FILTERS = {"all": 0, "positive_z": 1, "canvas": 2}
 

@@ -17,9 +17,17 @@ point, the construction of those tables, is done here in Python float64 exactly 
     frames = decode_images(vae, latents, post)            # (b, n_cam, H, W, 3) uint8, on the GPU
     pil = to_pil(frames)                                  # the 2-level list numpy_to_pil_double returns
 
-Writing files, encoding and FID stay with the caller.
+The reference then saves every view with `post_trans(img).save(<nuScenes name>.jpg)` and no options (val_set_gen.py:44,
+tools/downstream_v3_batched.py:244-252): libjpeg's baseline encoder at quality 75, 4:2:0 chroma, the standard Huffman
+tables.  That is integer arithmetic too, and `ops.jpeg_encode_u8` produces the same bytes on the device:
+
+    files = encode_jpeg(frames)                           # the 2-level list of `bytes`, one .jpg file each
+    save_jpeg(frames, paths)                              # ... written to `paths` (same nesting), directories created
+
+File decoding, PNG and FID stay with the caller.
 """
 import math
+import os
 
 import torch
 
@@ -176,3 +184,150 @@ def to_pil(u8):
     if arr.ndim == 4:
         return [Image.fromarray(a) for a in arr]
     return [[Image.fromarray(a) for a in scene] for scene in arr]
+
+
+# ---- JPEG: the header and the tables of the encoder ----------------------------------------------------------------------
+
+# ITU-T T.81 Annex K.1, natural (row-major) order: libjpeg's std_luminance_quant_tbl / std_chrominance_quant_tbl
+JPEG_BASE_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+                  14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+                  49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+JPEG_BASE_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+                    47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+# Annex K.3: (table class and id of the DHT segment, bits[1..16], values), in the order libjpeg writes them
+JPEG_HUFFMAN = (
+    (0x00, "00010501010101010100000000000000", "000102030405060708090a0b"),
+    (0x10, "0002010303020403050504040000017d",
+     "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a43"
+     "4445464748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2"
+     "b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa"),
+    (0x01, "00030101010101010101010000000000", "000102030405060708090a0b"),
+    (0x11, "00020102040403040705040400010277",
+     "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a"
+     "434445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9"
+     "aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa"),
+)
+JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21,
+               28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61,
+               54, 47, 55, 62, 63)                       # natural index of the i-th coefficient of the scan
+JPEG_MODES = "baseline, 4:2:0 chroma (subsampling 2), the standard Huffman tables, quality 1..100"
+
+_JPEG_HEADERS = {}                     # (h, w, quality) -> bytes
+_JPEG_DEVICE = {}                      # (h, w, quality, device) -> (header uint8, tables int32) on the device
+
+
+def _jpeg_quality(quality):
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError("quality must be an int in 1..100, got %r" % (quality,))
+    return quality
+
+
+def jpeg_quant_tables(quality):
+    """libjpeg's jpeg_set_quality: -> (luma, chroma), 64 values each in ZIGZAG order, as the DQT segments hold them and
+    as the kernels divide by them (times 8, the scale of the integer DCT)."""
+    q = _jpeg_quality(quality)
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple(tuple(min(max((base[k] * scale + 50) // 100, 1), 255) for k in JPEG_ZIGZAG)
+                 for base in (JPEG_BASE_LUMA, JPEG_BASE_CHROMA))
+
+
+def _jpeg_segment(marker, body):
+    return bytes((0xFF, marker)) + (len(body) + 2).to_bytes(2, "big") + body
+
+
+def jpeg_header(h, w, quality=75):
+    """The file up to and including SOS, in PIL's layout: SOI, JFIF 1.1 APP0 (unit 0, density 1 x 1), the two DQT
+    segments, SOF0 with sampling 2x2 / 1x1 / 1x1, the four DHT segments, SOS.  Host only, cached."""
+    h, w, quality = int(h), int(w), _jpeg_quality(quality)
+    if not (1 <= h <= 65535 and 1 <= w <= 65535):
+        raise ValueError("a JPEG frame is 1..65535 pixels on each side, got %d x %d" % (h, w))
+    key = (h, w, quality)
+    if key not in _JPEG_HEADERS:
+        out = b"\xff\xd8" + _jpeg_segment(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
+        for i, table in enumerate(jpeg_quant_tables(quality)):
+            out += _jpeg_segment(0xDB, bytes((i,)) + bytes(table))
+        out += _jpeg_segment(0xC0, b"\x08" + h.to_bytes(2, "big") + w.to_bytes(2, "big")
+                             + b"\x03\x01\x22\x00\x02\x11\x01\x03\x11\x01")
+        for tc_th, bits, vals in JPEG_HUFFMAN:
+            out += _jpeg_segment(0xC4, bytes((tc_th,)) + bytes.fromhex(bits) + bytes.fromhex(vals))
+        _JPEG_HEADERS[key] = out + _jpeg_segment(0xDA, b"\x03\x01\x00\x02\x11\x03\x11\x00\x3f\x00")
+    return _JPEG_HEADERS[key]
+
+
+def jpeg_tables(quality=75):
+    """What dd_jpeg_encode_u8 takes as `tables` (include/dualdiff_hip.h): int32 (672,) = the two quantisation tables of
+    jpeg_quant_tables, then per Huffman table of JPEG_HUFFMAN's DC pair and AC pair the entry (code << 8) | length of
+    every symbol (0 for a symbol the table does not have); codes assigned as T.81 Annex C does."""
+    words = [v for table in jpeg_quant_tables(quality) for v in table]
+    for want in (0x00, 0x01, 0x10, 0x11):                # dc luma, dc chroma, ac luma, ac chroma
+        _, bits, vals = next(t for t in JPEG_HUFFMAN if t[0] == want)
+        bits, vals = bytes.fromhex(bits), bytes.fromhex(vals)
+        entries = [0] * (16 if want < 0x10 else 256)
+        code = k = 0
+        for length in range(1, 17):
+            for _ in range(bits[length - 1]):
+                entries[vals[k]] = (code << 8) | length
+                code += 1
+                k += 1
+            code <<= 1
+        words += entries
+    return torch.tensor(words, dtype=torch.int32)
+
+
+def device_jpeg_tables(h, w, quality, device):
+    """(header uint8 (len,), tables int32 (672,)) of one (h, w, quality) on `device`, cached as device_tables does."""
+    device = torch.device(device)
+    key = (int(h), int(w), int(quality), device.type,
+           device.index if device.index is not None else torch.cuda.current_device())
+    if key not in _JPEG_DEVICE:
+        header = torch.frombuffer(bytearray(jpeg_header(h, w, quality)), dtype=torch.uint8)
+        _JPEG_DEVICE[key] = (header.to(device), jpeg_tables(quality).to(device))
+    return _JPEG_DEVICE[key]
+
+
+def _jpeg_options(options):
+    for name, value in options.items():
+        raise ValueError("JPEG option %s=%r is not built; available: %s" % (name, value, JPEG_MODES))
+
+
+@torch.no_grad()
+def encode_jpeg(u8, quality=75, **options):
+    """uint8 frames (b, n, H, W, 3) -> the 2-level list of `bytes` (one .jpg file per view, nested as to_pil nests its
+    images), (m, H, W, 3) -> a flat list: what `Image.fromarray(frame).save(f, "JPEG", quality=quality)` writes, byte
+    for byte, encoded on the GPU.  One readback of the lengths and one copy of the files' bytes; should a file not fit
+    the default capacity (header + H * W bytes), the call is repeated once with the capacity the lengths ask for."""
+    _jpeg_options(options)
+    if u8.dtype != torch.uint8 or u8.dim() not in (4, 5) or u8.shape[-1] != 3:
+        raise ValueError("encode_jpeg takes uint8 frames (b, n, H, W, 3) or (m, H, W, 3), got %s %s" % (tuple(u8.shape), u8.dtype))
+    frames = (u8.flatten(0, 1) if u8.dim() == 5 else u8).contiguous()
+    buf, lengths = O.jpeg_encode_u8(frames, quality)
+    n = lengths.cpu().tolist()
+    if max(n) > buf.shape[1]:
+        buf, lengths = O.jpeg_encode_u8(frames, quality, capacity=max(n))
+        n = lengths.cpu().tolist()
+    raw = buf[:, :max(n)].cpu().numpy()
+    files = [raw[i, :k].tobytes() for i, k in enumerate(n)]
+    if u8.dim() == 4:
+        return files
+    per = u8.shape[1]
+    return [files[i * per:(i + 1) * per] for i in range(u8.shape[0])]
+
+
+def save_jpeg(u8, paths, quality=75, **options):
+    """encode_jpeg, each file written to its path: `paths` nested as the frames are ((b, n) names, or m names).  Missing
+    directories are created, as the reference's `mkdir -p` does.  Returns the files' sizes, nested the same way."""
+    files = encode_jpeg(u8, quality, **options)
+    nested = u8.dim() == 5
+    rows = list(zip(files, paths)) if nested else [(files, paths)]
+    if len(paths) != len(files) or any(len(p) != len(f) for f, p in rows):
+        raise ValueError("save_jpeg takes one path per frame, nested as the frames are")
+    sizes = []
+    for fs, ps in rows:
+        for data, path in zip(fs, ps):
+            path = os.fspath(path)
+            if os.path.dirname(path):
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, "wb") as f:
+                f.write(data)
+        sizes.append([len(d) for d in fs])
+    return sizes if nested else sizes[0]

@@ -546,6 +546,32 @@ int dd_box_views(const float* corners, const float* filter_corners, const int64_
                  int64_t* classes, uint8_t* masks, int32_t* counts, int32_t* max_len, dd_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * JPEG output (csrc/jpeg.hip): the uint8 frames dd_image_resample_u8 / dd_image_quantize_u8 write -> the files the
+ * reference saves with PIL's `Image.save(<name>.jpg)` and no options (perception/data_prepare/val_set_gen.py:44,
+ * tools/downstream_v3_batched.py:244-252), byte for byte: libjpeg's baseline encoder, 4:2:0 chroma, the `islow` integer
+ * DCT, quantisation by 8 q rounding half away from zero, libjpeg's dummy blocks at the right and bottom edge.
+ *
+ * frames: uint8 [m][h][w][3] (device).  header: the file up to and including SOS, header_len bytes in DEVICE memory, built
+ * by the caller once per (h, w, quality) (pipeline/image_output.py: jpeg_header).  tables: uint32 [672] (device), from the
+ * same place as the header's DQT segments:
+ *   [0, 128)    q[2][64]: the luma and chroma quantisation values in zigzag order, as DQT holds them
+ *   [128, 160)  dc[2][16]: Huffman entry (code << 8) | length of DC size s, luma then chroma
+ *   [160, 672)  ac[2][256]: the entry of AC symbol (run << 4) | size
+ * (a q outside 1..65535 and a length above 16 are clamped: no table contents make the kernels leave their buffers).
+ * out: uint8 [m][capacity], row i = file i; lengths: int32 [m], the TRUE length of file i also when it exceeds capacity —
+ * the row then holds the first `capacity` bytes of the file and nothing is written outside it.
+ * workspace: at least dd_jpeg_workspace_bytes(m, h, w) bytes, 16-byte aligned, contents don't care before and after.
+ * Six launches on `stream` whatever m and the content are, no host synchronisation: the call can be captured in a graph.
+ * DD_ERR_BAD_ARG, before any runtime call: a NULL pointer, m / h / w / header_len <= 0, h or w above 65535, capacity <
+ * header_len + 2, a misaligned workspace / tables / lengths, workspace_bytes too small.  m > 65535 or more than 262144
+ * MCUs (16 x 16 pixels) per frame: DD_ERR_UNSUPPORTED; dd_jpeg_workspace_bytes returns -1 for either kind.
+ * ------------------------------------------------------------------------- */
+int64_t dd_jpeg_workspace_bytes(int32_t m, int32_t h, int32_t w);
+int dd_jpeg_encode_u8(const uint8_t* frames, int32_t m, int32_t h, int32_t w, const uint8_t* header, int32_t header_len,
+                      const uint32_t* tables, void* workspace, int64_t workspace_bytes, uint8_t* out, int64_t capacity,
+                      int32_t* lengths, dd_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * CLIP text encoder (csrc/clip.hip): the SD-v1.5 `text_encoder` (transformers.CLIPTextModel) that the reference calls at
  * runner/base_runner.py:119,511-514, runner/multiview_runner.py:145,427-428 (`text_encoder(ids)[0]`), through diffusers'
  * _encode_prompt at pipeline/pipeline_bev_controlnet.py:273 and at networks/bbox_embedder.py:133-145
