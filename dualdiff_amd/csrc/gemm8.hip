@@ -5,6 +5,7 @@
 //
 // A8 / W8: OCP e4m3fn bytes with a per-row / per-output-channel fp32 scale (symmetric, amax / 448).  The activations are
 // quantised by the LayerNorm that produces them (dd_rowquant_fp8: the LayerNorm launch the 16-bit path has anyway).
+// A row with a NaN or an Inf in it carries a_scale = NaN and so leaves the GEMM as a NaN row (see dd_rowquant_fp8_kernel).
 //
 // Why it is faster than the 16-bit projection, not just smaller: this build's tiled GEMMs are bound by L2 -> LDS staging
 // bytes and by LDS fragment reads; fp8 halves both per multiply-accumulate, and
@@ -200,8 +201,12 @@ void dd_gemm8_kernel(const Gemm8Params p) {
 
 // ---- row quantisation (optionally behind a LayerNorm): T [rows][c] -> e4m3 [rows][ldq] + fp32 scale[rows] -------------
 // One wave per row.  y = LayerNorm(x) (two-pass fp32 statistics, result ROUNDED to T exactly as dd_layernorm stores it) or
-// y = x; scale = max|y| / 448 (1 for an all-zero row); q = e4m3(clamp(y / scale, +-448)), round-to-nearest-even; the
-// padding columns c .. ldq - 1 are zero.
+// y = x; in IEEE fp32: amax = max|y|, sc = max(amax / 448, 2^-126) (1 for an all-zero row), inv = 1 / sc,
+// t = clamp(y * inv, +-448), q = e4m3(t), round-to-nearest-even; scale = sc; the padding columns c .. ldq - 1 are zero.
+// The floor keeps inv finite for every finite nonzero row (a bf16 row below 448 * 2^-126 ~ 5.3e-36 would otherwise get
+// inv = inf and 0 * inf = NaN in place of its zeros); it changes no row above that.  A row of y that holds a NaN or an
+// Inf gets scale = NaN and zero bytes: dd_gemm8 then returns that row as NaN in every column, as the 16-bit path
+// (LayerNorm, then GEMM) would, instead of finite numbers made of saturated bytes.
 template <typename T, int NV>
 __global__ __launch_bounds__(256)
 void dd_rowquant_fp8_kernel(const T* __restrict__ x, const T* __restrict__ gamma, const T* __restrict__ beta,
@@ -247,14 +252,17 @@ void dd_rowquant_fp8_kernel(const T* __restrict__ x, const T* __restrict__ gamma
       }
     }
   }
-  float amax = 0.f;
+  float amax = 0.f, nf = 0.f;                                  // nf: 0 while every element is finite, NaN after a NaN or Inf
 #pragma unroll
   for (int i = 0; i < NV; ++i)
 #pragma unroll
-    for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(v[i][e]));
+    for (int e = 0; e < 8; ++e) { amax = fmaxf(amax, fabsf(v[i][e])); nf += v[i][e] * 0.f; }
   amax = dd_wave_max(amax);
-  const float sc = amax > 0.f ? amax / 448.0f : 1.0f;
-  const float inv = 1.0f / sc;
+  const bool bad = __any(nf != nf);                             // fmaxf drops a NaN: the row says so in its scale instead
+  // the floor keeps 1 / sc finite for rows down to the subnormals (amax / 448 would be subnormal below 448 * 2^-126);
+  // no row with amax >= 448 * 2^-126 ~ 5.3e-36 is touched by it
+  const float sc = bad ? __builtin_nanf("") : amax > 0.f ? fmaxf(amax / 448.0f, 0x1p-126f) : 1.0f;
+  const float inv = bad ? 0.f : 1.0f / sc;
   if (lane == 0) scale[row] = sc;
   const int nq = (int)(ldq >> 3);                              // 8-byte groups of the padded row
 #pragma unroll
@@ -265,7 +273,7 @@ void dd_rowquant_fp8_kernel(const T* __restrict__ x, const T* __restrict__ gamma
     if (i < NV && vi < nvec) {
       float t[8];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) t[e] = fminf(fmaxf(v[i < NV ? i : 0][e] * inv, -448.0f), 448.0f);
+      for (int e = 0; e < 8; ++e) t[e] = bad ? 0.f : fminf(fmaxf(v[i < NV ? i : 0][e] * inv, -448.0f), 448.0f);
       lo = __builtin_amdgcn_cvt_pk_fp8_f32(t[0], t[1], lo, false);
       lo = __builtin_amdgcn_cvt_pk_fp8_f32(t[2], t[3], lo, true);
       hi = __builtin_amdgcn_cvt_pk_fp8_f32(t[4], t[5], hi, false);

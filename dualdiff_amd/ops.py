@@ -1222,7 +1222,9 @@ def quantize_fp8_padded(w):
 
 def rowquant_fp8(x, norm=None):
     """Per-row e4m3fn quantisation of the activations (dd_rowquant_fp8), optionally behind LayerNorm `norm =
-    (gamma, beta, eps)` in the same launch -> (float8_e4m3fn [rows, k rounded up to 128], fp32 scale [rows])."""
+    (gamma, beta, eps)` in the same launch -> (float8_e4m3fn [rows, k rounded up to 128], fp32 scale [rows]).
+    scale = max(amax / 448, 2^-126), 1 for a zero row; a row that holds a NaN or an Inf (behind the LayerNorm: anywhere in
+    it) gets scale = NaN, which gemm8 turns into a NaN output row."""
     lib = _native.load()
     _need_gpu(x)
     x = _rows2d(x)

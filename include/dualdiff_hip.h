@@ -677,9 +677,12 @@ int dd_given_views_noise(void* x, void* x_dup, const uint8_t* given, const float
  * EXTENSION (BASELINE configs[4]: "fp8 weights (CDNA4 fp8 MFMA)"; no reference semantics — README.md:47-49 is prose):
  * W8A8 projection on the fp8 matrix path.
  *   dd_rowquant_fp8: y = gamma ? LayerNorm(x) (dd_layernorm's arithmetic, rounded to the storage type) : x;
- *       scale[r] = max_c |y[r, c]| / 448 (1 for a zero row);  q[r, c] = e4m3fn(y[r, c] / scale[r]) (round to nearest even);
- *       q rows have pitch ldq bytes (multiple of 128, zero padded) — the LayerNorm launch of norm1 / norm2 / norm4
- *       (networks/blocks.py:150-222) doubles as the activation quantiser.
+ *       scale[r] = max(max_c |y[r, c]| / 448, 2^-126) (1 for a zero row; the floor keeps 1 / scale finite for every finite
+ *       nonzero row and changes none above 448 * 2^-126);  q[r, c] = e4m3fn(clamp(y[r, c] * (1 / scale[r]), +-448)) in IEEE
+ *       fp32, round to nearest even;  q rows have pitch ldq bytes (multiple of 128, ldq - c < 512, bytes c .. ldq - 1
+ *       zero) — the LayerNorm launch of norm1 / norm2 / norm4 (networks/blocks.py:150-222) doubles as the activation
+ *       quantiser.  A row of y that holds a NaN or an Inf gets scale[r] = NaN (its bytes are finite codes): dd_gemm8
+ *       returns such a row as NaN in every column, as LayerNorm followed by the 16-bit GEMM would.
  *   dd_gemm8: out[r, n] = a_scale[r] * w_scale[n] * sum_k A8[r, k] W8[n, k] + bias[n] + res[r, n], fp32 accumulation in
  *       v_mfma_scale_f32_16x16x128_f8f6f4 (unit block scales), A8 [rows][lda] / W8 [n][ldw] OCP e4m3fn bytes whose rows are
  *       zero padded to k_padded (multiple of 128); output in `dtype`, row-major or head-major planes as dd_gemm's
