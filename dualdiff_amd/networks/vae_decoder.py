@@ -66,12 +66,26 @@ class VaeAttention(_Cached):
         qk = O.gemm(t, wqk, bqk)                                     # (m*hw, 2C): q | k
         out = torch.empty_like(x)
         wv = self.to_v.weight.detach()
+        # The key count is the N of the logits GEMM and of V^T and the K of P @ V, and dd_gemm takes multiples of 8 there:
+        # a token count that is none (a 3 x 5 latent: 15) gets zero key rows and zero token rows up to the next one, in
+        # two buffers of this call.  The softmax reads the hw real logits of a row (ragged length, padded pitch) and
+        # writes zero probabilities behind them; V^T of a zero token row is a zero column.
+        hwp = (hw + 7) // 8 * 8
+        kp = tp = None
+        if hwp != hw:
+            kp, tp = x.new_zeros((hwp, c)), x.new_zeros((hwp, c))
         for i in range(m):                                           # one view at a time: 1 head, hw tokens
             rows = slice(i * hw, (i + 1) * hw)
-            q, k = qk[rows, :c], qk[rows, c:]
-            s = O.gemm(q, k.contiguous(), alpha=self.scale, out_f32=True)           # (hw, hw) fp32 logits
-            p = O.softmax_rows(s, x.dtype)                                          # (hw, hw) probabilities
-            vt = O.gemm(wv, t[rows])                                                # V^T (C, hw), bias added below
+            q, k, ti = qk[rows, :c], qk[rows, c:], t[rows]
+            if kp is None:
+                k = k.contiguous()
+            else:
+                kp[:hw].copy_(k)
+                tp[:hw].copy_(ti)
+                k, ti = kp, tp
+            s = O.gemm(q, k, alpha=self.scale, out_f32=True)                        # (hw, hwp) fp32 logits
+            p = O.softmax_rows(s[:, :hw], x.dtype)                                  # (hw, hwp) probabilities
+            vt = O.gemm(wv, ti)                                                     # V^T (C, hwp), bias added below
             o = O.gemm(p, vt, self.to_v.bias)                                       # P V + b_v
             O.gemm(o, self.to_out[0].w2d, self.to_out[0].bias, res=x[rows], out=out[rows])
         return out
