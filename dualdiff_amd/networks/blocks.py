@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops as O
+from .._consts import device_const
 from .._native import Unsupported
 from . import layers
 from .layers import Attention, BasicTransformerBlock, LayerNorm, Linear, want_ln_stats
@@ -80,7 +81,7 @@ class BasicMultiviewTransformerBlock(BasicTransformerBlock):
             self.connector = None
         else:
             raise TypeError("Unknown zero module type: %s" % zero_module_type)
-        self._maps = {}
+        self._pair_key = tuple((v, tuple(nb)) for v, nb in sorted(self.neighboring_view_pair.items()))
         # dualdiff_amd.parallel.ViewShard when the views of a scene are spread over several GPUs
         # (UNet2DConditionModelMultiview.set_view_shard); None = all n_cam views are local
         self.view_shard = None
@@ -121,17 +122,14 @@ class BasicMultiviewTransformerBlock(BasicTransformerBlock):
         return ret
 
     def neighbour_maps(self, batch, device):
-        """int32 [batch] maps: instance b*n_cam+v -> instance of its k-th neighbour."""
-        key = (batch, str(device))
-        if key not in self._maps:
-            n = self.n_cam
-            depth = max(len(v) for v in self.neighboring_view_pair.values())
-            maps = []
-            for j in range(depth):
-                idx = [(i // n) * n + self.neighboring_view_pair[i % n][j] for i in range(batch)]
-                maps.append(torch.tensor(idx, dtype=torch.int32, device=device))
-            self._maps[key] = maps
-        return self._maps[key]
+        """int32 [batch] maps: instance b*n_cam+v -> instance of its k-th neighbour.  Device constants keyed by the view
+        pairs and the batch (_consts.device_const): blocks with the same pairs share them."""
+        def build():
+            n, pair = self.n_cam, self.neighboring_view_pair
+            depth = max(len(v) for v in pair.values())
+            return tuple(torch.tensor([(i // n) * n + pair[i % n][j] for i in range(batch)], dtype=torch.int32)
+                         for j in range(depth))
+        return device_const(("neighbour_maps", self._pair_key, batch), device, build)
 
     def _attn4_sharded(self, h, batch, l):
         """attn4 when this rank holds only `n_local` of the n_cam views (SURVEY §8e view split): Q/K/V of

@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from .. import ops as O
 from .. import upfold
+from .._consts import device_const
 
 
 # ----------------------------------------------------------------------------- helpers ----
@@ -130,19 +131,12 @@ def lk_dev_for(ctx2d, lk):
     return cur[3]
 
 
-_LK_CONST = {}
-
-
 def lk_const(value, device):
-    """int32 device tensor [1] holding `value` — one per (device, value), created outside any capture and kept for the
-    life of the process (a forward graph copies it into its own static word, an eager call reads it in place)."""
-    key = (str(device), int(value))
-    t = _LK_CONST.get(key)
-    if t is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("lk_const(%d) first requested inside a stream capture" % value)
-        t = _LK_CONST[key] = torch.tensor([int(value)], dtype=torch.int32, device=device)
-    return t
+    """int32 device tensor [1] holding `value` — a device constant (_consts.device_const: one per device and value,
+    first asked for outside any capture; a forward graph copies it into its own static word, an eager call reads it in
+    place)."""
+    value = int(value)
+    return device_const(("lk", value), device, lambda: torch.tensor([value], dtype=torch.int32))
 
 
 def _pad_cols(w, mult=8):

@@ -14,9 +14,12 @@ import os as _os
 import torch
 
 from . import _native, _timer, _workspace, tuning, upfold as _upfold
+from ._consts import device_const
 from ._native import DD_BF16, DD_EPI_GEGLU, DD_EPI_NONE, DD_EPI_SILU, DD_F16, AttnDesc, Gemm8Desc, GemmDesc, XAttnDesc
 from ._timer import KernelTimer, _stream, set_timer  # noqa: F401
 from ._workspace import workspace, workspace_owner  # noqa: F401
+from .image_tables import (_image_lut, _image_mean_std, device_jpeg_tables, device_tables,  # noqa: F401
+                           image_norm_lut, jpeg_header)
 from .tuning import (CHALLENGE_TILES, TUNE_TABLE_PATH, forget_tuned, load_tuned, save_tuned,  # noqa: F401
                      tune_candidates, tuned_table)
 
@@ -33,7 +36,6 @@ LN_OUT_TILE = int(_os.environ.get("DD_LN_OUT_TILE", "0"))
 # profiles/r03_sfa_roofline.txt).  Above this many workgroups the callers take the three launches.
 XATTN_MAX_WGS = int(_os.environ.get("DD_XATTN_MAX_WGS", "256"))
 CAUSAL_ATTN_MAX_L = 128         # DD_CAUSAL_ATTN_MAX_L of include/dualdiff_hip.h
-_ZERO_BIAS = {}
 _FDT = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}
 
 
@@ -395,8 +397,7 @@ def image_resample_u8(x, size, padding=(0, 0, 0, 0), fill=0, m11=False, out=None
     """PIL's `Image.resize(size[::-1], BICUBIC)` and torchvision's `Pad(padding, fill)` of the quantised images, byte for
     byte and in one launch (dd_image_resample_u8): x (m, 3, h, w) as image_quantize_u8 takes it, size = (h, w) of the
     resize, padding = (left, top, right, bottom) or Pad's shorter forms -> (m, top + h + bottom, left + w + right, 3)
-    uint8.  The coefficient tables are built on the host once per size pair and kept per device
-    (pipeline.image_output.device_tables): call once before capturing the launch in a graph."""
+    uint8.  The coefficient tables (image_tables.device_tables) are device constants under the rule of _consts."""
     m, h, w = _image_arg(x, "image_resample_u8")
     try:
         oh, ow = (int(v) for v in size)
@@ -410,7 +411,6 @@ def image_resample_u8(x, size, padding=(0, 0, 0, 0), fill=0, m11=False, out=None
     out = _image_out(out, (m, pt + oh + pb, pl + ow + pr, 3), x.device, "image_resample_u8")
     _need_gpu(x, out)
     lib = _native.load()
-    from .pipeline.image_output import device_tables
     kx, bx = device_tables(w, ow, x.device)
     ky, by = device_tables(h, oh, x.device)
     _timer.launch("image_resample_u8", lib.dd_image_resample_u8, _ptr(x), _ptr(out), m, h, w, oh, ow, _ptr(kx), _ptr(bx),
@@ -420,37 +420,7 @@ def image_resample_u8(x, size, padding=(0, 0, 0, 0), fill=0, m11=False, out=None
     return out
 
 
-_IMAGE_LUTS = {}                # (mean, std, device) -> float32 (3, 256) on the device
 _IMAGE_LAYOUTS = {"nchw": 0, "nhwc8": 1}
-
-
-def _image_mean_std(mean, std):
-    try:
-        mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
-    except (TypeError, ValueError):
-        raise ValueError("mean and std must be 3 numbers each, got %r / %r" % (mean, std))
-    if len(mean) != 3 or len(std) != 3:
-        raise ValueError("mean and std must be 3 numbers each, got %r / %r" % (mean, std))
-    if any(v == 0 for v in std):
-        raise ValueError("std must not be 0 (Normalize would divide by zero), got %r" % (std,))
-    return mean, std
-
-
-def image_norm_lut(mean, std):
-    """torchvision's ToTensor + Normalize on every byte value, with torch's own float32 ops: (3, 256) float32 on the host,
-    lut[c, b] = (b / 255 - mean[c]) / std[c]."""
-    mean, std = _image_mean_std(mean, std)
-    x = torch.arange(256).float().div(255)                   # ToTensor
-    mean, std = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
-    return x[None].sub(mean[:, None]).div(std[:, None]).contiguous()      # Normalize: float32 tensors, as torchvision's
-
-
-def _image_lut(mean, std, device):
-    key = (mean, std, device.type,
-           device.index if device.index is not None else torch.cuda.current_device())
-    if key not in _IMAGE_LUTS:
-        _IMAGE_LUTS[key] = image_norm_lut(mean, std).to(device)
-    return _IMAGE_LUTS[key]
 
 
 def image_load_u8(frames, size, box=None, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), dtype=torch.float32, layout="nchw",
@@ -460,8 +430,7 @@ def image_load_u8(frames, size, box=None, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0
     of the resize, box = PIL's (left, top, right, bottom) inside the resized image (default: all of it), dtype fp16 /
     bf16 / fp32.  layout "nchw" -> (m, 3, bottom - top, right - left); "nhwc8" -> (m * rows * cols, 8) channels-last
     with channels 3..7 zero, what `nchw_to_nhwc(x, 8)` hands to the VAE encoder's conv_in.  Only the crop is computed.
-    The coefficient tables and the normalisation table are built on the host once per size pair / (mean, std) and kept
-    per device: call once before capturing the launch in a graph."""
+    The coefficient tables and the normalisation table (image_tables) are device constants under the rule of _consts."""
     what = "image_load_u8"
     if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
         raise ValueError("%s takes an (m, h, w, 3) frame batch, got %s" % (what, tuple(frames.shape)))
@@ -499,7 +468,6 @@ def image_load_u8(frames, size, box=None, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0
     _need_gpu(frames, out)
     _forget_derived(out)
     lib = _native.load()
-    from .pipeline.image_output import device_tables
     kx, bx = device_tables(w, nw, frames.device)
     ky, by = device_tables(h, nh, frames.device)
     lut = _image_lut(mean, std, frames.device)
@@ -515,9 +483,9 @@ def jpeg_encode_u8(frames, quality=75, out=None, capacity=None):
     (dd_jpeg_encode_u8): baseline, 4:2:0 chroma, the standard Huffman tables.  -> (buf (m, capacity) uint8, lengths (m,)
     int32), both on the device: file i is buf[i, :lengths[i]].  capacity defaults to header + H * W bytes per frame (at least the header and the end marker); a
     length above the capacity is the file's true length, the row then holds its first `capacity` bytes.  Nothing is read
-    back.  The header and the tables are built on the host once per (H, W, quality) and kept per device
-    (pipeline.image_output.device_jpeg_tables), the scratch buffer is ops.workspace's: call once, on the capture stream or
-    under the same workspace_owner, before capturing the launches in a graph."""
+    back.  The header and the tables (image_tables.device_jpeg_tables) are device constants under the rule of _consts;
+    the scratch buffer is ops.workspace's: call once, on the capture stream or under the same workspace_owner, before
+    capturing the launches in a graph."""
     what = "jpeg_encode_u8"
     if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
         raise ValueError("%s takes an (m, H, W, 3) frame batch, got %s" % (what, tuple(frames.shape)))
@@ -530,7 +498,6 @@ def jpeg_encode_u8(frames, quality=75, out=None, capacity=None):
     m, h, w = frames.shape[0], frames.shape[1], frames.shape[2]
     if h > 65535 or w > 65535:
         raise ValueError("%s: a JPEG frame is at most 65535 x 65535, got %d x %d" % (what, h, w))
-    from .pipeline.image_output import device_jpeg_tables, jpeg_header
     header_len = len(jpeg_header(h, w, quality))
     if out is not None:
         if out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != m or not out.is_contiguous():
@@ -823,6 +790,10 @@ def _xpacked(w):
     return w if w.dim() == 1 and w.numel() == 320 * 320 else xattn_pack_weight(w)
 
 
+def _zero_bias(dtype, device):
+    return device_const(("zero_bias", dtype), device, lambda: torch.zeros(320, dtype=dtype))
+
+
 def xattn320(x, wq, wo, bo, k, v, instances, rows_per_inst, lk, scale, *, res=None, ln_out=None, out=None, lk_dev=None):
     """Fused q-projection -> attention over the lk context keys of each view-instance -> out-projection + bias +
     residual, one launch (include/dualdiff_hip.h: dd_xattn320).  x: (instances * rows_per_inst, 320); k / v: either
@@ -857,10 +828,7 @@ def xattn320(x, wq, wo, bo, k, v, instances, rows_per_inst, lk, scale, *, res=No
         d.res, d.ldres = res.data_ptr(), res.stride(0)
     d.wq, d.wo = wqp.data_ptr(), wop.data_ptr()
     if bo is None:                      # the kernel loads the bias unconditionally (a conditional load would be waited for in place)
-        key = (x.dtype, x.device)
-        if key not in _ZERO_BIAS:
-            _ZERO_BIAS[key] = torch.zeros(320, dtype=x.dtype, device=x.device)
-        bo = _ZERO_BIAS[key]
+        bo = _zero_bias(x.dtype, x.device)
     d.bo = bo.data_ptr()
     d.k, d.ldk, d.k_inst_stride, d.k_head_stride = kv_operand(k)
     d.v, d.ldv, d.v_inst_stride, d.v_head_stride = kv_operand(v)

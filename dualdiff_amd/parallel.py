@@ -13,6 +13,8 @@ exchange step on that path (pipeline_bev_controlnet.py:487-490 combines the halv
 import torch
 import torch.distributed as dist
 
+from ._consts import device_const
+
 
 def shard_scenes(n_scenes, rank, world):
     """Contiguous, balanced slice [lo, hi) of scene indices for `rank` (first ranks take the remainder)."""
@@ -279,7 +281,8 @@ class ViewShard:
     def __init__(self, plan, exchange=None):
         self.plan = plan
         self._exchange = exchange if exchange is not None else HaloExchange(plan)
-        self._maps = {}
+        # what plan.kv_maps depends on: the constants are keyed by content, equal plans share them
+        self._maps_key = (tuple((v, tuple(nb)) for v, nb in sorted(plan.pair.items())), tuple(plan.local), tuple(plan.remote))
         self.segmenter = None        # a SegmentedGraph while the step is being recorded / replayed in segments
 
     def exchange(self, kv):
@@ -298,10 +301,9 @@ class ViewShard:
         return len(self.plan.local)
 
     def maps(self, nb, device):
-        key = (nb, str(device))
-        if key not in self._maps:
-            self._maps[key] = [torch.tensor(m, dtype=torch.int32, device=device) for m in self.plan.kv_maps(nb)]
-        return self._maps[key]
+        """plan.kv_maps(nb) as int32 tensors on `device`: device constants (_consts.device_const)."""
+        return device_const(("kv_maps", self._maps_key, nb), device,
+                            lambda: tuple(torch.tensor(m, dtype=torch.int32) for m in self.plan.kv_maps(nb)))
 
     # ---- input slicing (sampler level) -------------------------------------------------------
     def take_views(self, t, dim, n_cam=None):
