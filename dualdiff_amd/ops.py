@@ -527,6 +527,62 @@ def jpeg_encode_u8(frames, quality=75, out=None, capacity=None):
     return out, lengths
 
 
+JPEG_DECODE_TABLE_BYTES = 4016      # the table block of one frame (csrc/jpeg_decode_core.h: DdJdTables)
+JPEG_DECODE_SAMPLINGS = (420, 444)
+JPEG_DECODE_STATUS = ((1, "the stream is exhausted before the last block"), (2, "an invalid Huffman code"),
+                      (4, "a zero run past coefficient 63"), (8, "bytes left behind the last block"))
+
+
+def jpeg_decode_u8(scan, offsets, lengths, tables, h, w, sampling, max_scan_bytes, rounds=None, out=None):
+    """The entropy-coded segments of m baseline JPEG files of one geometry -> (frames (m, h, w, 3) uint8, status (m,)
+    int32), both on the device, the frames byte for byte PIL's `Image.open(f).convert("RGB")` (dd_jpeg_decode_u8).
+    scan: uint8 (n,), the segments still byte-stuffed, frame i at scan[offsets[i] : offsets[i] + lengths[i]] at any byte
+    alignment; offsets, lengths: int32 (m,); tables: uint8 (m, 4016), one block per frame
+    (pipeline/jpeg_input.py: table_block) — all device tensors, usually views of one upload.  sampling: 420 or 444;
+    max_scan_bytes: at least every length (the host knows them; nothing is read back).  status[i] is 0 or an OR of
+    JPEG_DECODE_STATUS's bits; a bad frame leaves the others alone.  rounds: None for the library's default; the frames
+    do not depend on it.  The scratch buffer is ops.workspace's: call once before capturing the launches in a graph."""
+    what = "jpeg_decode_u8"
+    if scan.dtype != torch.uint8 or scan.dim() != 1 or scan.numel() == 0 or not scan.is_contiguous():
+        raise ValueError("%s takes the scan bytes as a contiguous uint8 (n,) tensor, got %s %s" % (what, tuple(scan.shape), scan.dtype))
+    m = offsets.numel()
+    for name, t in (("offsets", offsets), ("lengths", lengths)):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != m or m == 0 or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous int32 (m,) tensor, got %s %s" % (what, name, tuple(t.shape), t.dtype))
+    if tables.dtype != torch.uint8 or tuple(tables.shape) != (m, JPEG_DECODE_TABLE_BYTES) or not tables.is_contiguous():
+        raise ValueError("%s: tables must be a contiguous uint8 (%d, %d) tensor, got %s %s"
+                         % (what, m, JPEG_DECODE_TABLE_BYTES, tuple(tables.shape), tables.dtype))
+    ints = (h, w, sampling, max_scan_bytes) + (() if rounds is None else (rounds,))
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in ints):
+        raise ValueError("%s: h, w, sampling, max_scan_bytes and rounds are ints" % what)
+    if not (1 <= h <= 65535 and 1 <= w <= 65535):
+        raise ValueError("%s: a JPEG frame is 1 x 1 to 65535 x 65535, got %d x %d" % (what, h, w))
+    if sampling not in JPEG_DECODE_SAMPLINGS:
+        raise ValueError("%s: sampling must be one of %s, got %r" % (what, JPEG_DECODE_SAMPLINGS, sampling))
+    if max_scan_bytes <= 0:
+        raise ValueError("%s: max_scan_bytes must be positive, got %d" % (what, max_scan_bytes))
+    if rounds is not None and not 0 <= rounds <= 64:
+        raise ValueError("%s: rounds must be in 0..64, got %d" % (what, rounds))
+    out = _image_out(out, (m, h, w, 3), scan.device, what)
+    _need_gpu(scan, offsets, lengths, tables, out)
+    if tables.data_ptr() % 4 or offsets.data_ptr() % 4 or lengths.data_ptr() % 4:
+        raise ValueError("%s: tables, offsets and lengths must start on a 4-byte boundary" % what)
+    status = torch.empty((m,), dtype=torch.int32, device=scan.device)
+    lib = _native.load()
+    need = lib.dd_jpeg_decode_workspace_bytes(m, h, w, sampling, max_scan_bytes)
+    if need < 0:
+        raise _native.Unsupported("dualdiff_amd.%s: %d frames of %d x %d with segments of %d bytes are more than one call takes"
+                                  % (what, m, h, w, max_scan_bytes))
+    ws = workspace(need, scan.device, kind="jpeg_decode")
+    _timer.launch(what, lib.dd_jpeg_decode_u8, _ptr(scan), scan.numel(), _ptr(offsets), _ptr(lengths), max_scan_bytes,
+                  _ptr(tables), m, h, w, sampling, _ptr(out), _ptr(status), _ptr(ws), ws.numel() * 4,
+                  -1 if rounds is None else rounds, _stream(),
+                  # the segments read twice and written once without stuffing, the frames written; the decode passes read what
+                  # the content makes them read and are not booked
+                  book=lambda: ("dd_jpeg_decode", 0.0, float(3 * scan.numel() + out.numel())))
+    return out, status
+
+
 BOX_POINT_MODES = {"all-xyz": 0, "cxyz": 1}      # dataset/utils.py:222-226; points per box 8 / 4
 BOX_FILTERS = {"all": 0, "positive_z": 1, "canvas": 2}
 

@@ -25,7 +25,8 @@ float32 ops.
     pixel_values = pre(frames)                                       # (b, n_cam, 900, 1600, 3) uint8 -> (b, n_cam, 3, fH, fW)
     latents = encode_images(vae, frames, pre, given=given)           # == encode_pixel_values(vae, pre(frames), ...)
 
-Decoding JPEG files, and the flip and rotation of ImageAug3D's training mode, stay with the caller.
+The frames come from the camera files through pipeline/jpeg_input.py (decode_jpeg / load_jpeg); the flip and rotation of
+ImageAug3D's training mode stay with the caller.
 """
 import torch
 

@@ -24,7 +24,7 @@ tables.  That is integer arithmetic too, and `ops.jpeg_encode_u8` produces the s
     files = encode_jpeg(frames)                           # the 2-level list of `bytes`, one .jpg file each
     save_jpeg(frames, paths)                              # ... written to `paths` (same nesting), directories created
 
-File decoding, PNG and FID stay with the caller.
+The way back, .jpg files to uint8 frames, is pipeline/jpeg_input.py.  PNG and FID stay with the caller.
 """
 import os
 

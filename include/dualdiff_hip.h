@@ -572,6 +572,58 @@ int dd_jpeg_encode_u8(const uint8_t* frames, int32_t m, int32_t h, int32_t w, co
                       int32_t* lengths, dd_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * JPEG input (csrc/jpeg_decode.hip, csrc/jpeg_decode_core.h): the entropy-coded segments of m baseline .jpg files of one
+ * geometry -> uint8 frames [m][h][w][3] (device), byte for byte what PIL's `Image.open(f).convert("RGB")` returns for
+ * the camera files the reference opens (configs/dataset/Nuscenes.yaml:98,183 LoadMultiViewImageFromFiles,
+ * networks/occ3d_proj.py:124, tools/fid_score.py:79): libjpeg's Huffman decoder, the `islow` integer inverse DCT, the
+ * "fancy" triangle chroma upsampling (plain 2 x 2 replication where the chroma plane is at most two columns wide, i.e. for
+ * 4:2:0 frames of width 1..4, as jdsample.c chooses), the 16-bit fixed-point colour conversion.  The host reads the files' headers only
+ * (pipeline/jpeg_input.py: parse_jpeg); no pass over the scan bytes runs there.
+ *
+ * scan: scan_bytes bytes (device) that hold every frame's segment — the bytes between SOS and EOI, still byte-stuffed —
+ * frame i at scan + offsets[i], lengths[i] bytes, at any byte alignment; offsets / lengths: int32 [m] (device).  Every
+ * read is clamped to [0, scan_bytes) and to max_scan_bytes per frame, whatever offsets and lengths hold.
+ * tables: one block of 4016 bytes per frame (device, 4-byte aligned), little-endian, as jpeg_input.table_block builds it:
+ *   [0, 384)      uint16 q[3][64]: the quantisation values of component Y, Cb, Cr in natural (row-major) order
+ *   [384, 392)    uint8 tdc[3], tac[3]: the DC / AC Huffman table (0 or 1) of each component; 2 bytes of padding
+ *   [392, 4008)   four Huffman tables of 904 bytes, DC 0, DC 1, AC 0, AC 1:
+ *                   uint16 lut[256]  the next 8 bits -> (code length << 8) | symbol, 0 for a code longer than 8 bits
+ *                   int32 lim[17]    lim[l] = (the largest code of length <= l, plus 1) << (16 - l)
+ *                   int32 off[17]    symbol of a code of length l = vals[off[l] + (next 16 bits >> (16 - l))]
+ *                   uint8 vals[256]
+ *   [4008, 4016)  padding
+ * (no table contents make the kernels leave their buffers: lengths are clamped, indices masked).
+ * sampling: 420 (luma 2 x 2, chroma 1 x 1) or 444 (all 1 x 1).  out: uint8 [m][h][w][3], any alignment; only rows below h
+ * and columns below w are stored.  status: int32 [m], per frame 0 or an OR of DD_JPEG_EXHAUSTED (the stream ended before
+ * the frame's last block), DD_JPEG_BAD_CODE (a bit pattern in no table, or a symbol baseline does not have),
+ * DD_JPEG_BAD_RUN (a zero run past coefficient 63), DD_JPEG_TRAILING (a byte or more of the stream is left behind the
+ * last block: libjpeg decodes such a file with a warning, this decoder leaves it to the caller); the frame's pixels are
+ * then unspecified, the other frames' are not affected.
+ * rounds: how often every subsequence of DD_JPEG_SUB_BITS bits is decoded again from its left neighbour's exit state
+ * before the in-order repair pass decodes whatever is still not proven; 0..64, or -1 for DD_JPEG_DECODE_ROUNDS.  The
+ * result does not depend on it (0 sends the whole stream through the repair pass); it is there for tests and timing.
+ * workspace: at least dd_jpeg_decode_workspace_bytes(m, h, w, sampling, max_scan_bytes) bytes, 16-byte aligned, contents
+ * don't care before and after; max_scan_bytes >= every lengths[i].
+ * One memset and 9 + rounds launches on `stream` (a round whose subsequences all stand costs about 5 us), whatever m and the content are; no host synchronisation, no waiting
+ * between workgroups: the call can be captured in a graph.
+ * DD_ERR_BAD_ARG, before any runtime call: a NULL pointer, m / h / w / scan_bytes / max_scan_bytes <= 0, h or w above
+ * 65535, a sampling other than 420 / 444, rounds outside -1..64, a misaligned workspace / tables / offsets / lengths /
+ * status, workspace_bytes too small.  m > 65535, more than 262144 MCUs per frame or max_scan_bytes above 2^27:
+ * DD_ERR_UNSUPPORTED; dd_jpeg_decode_workspace_bytes returns -1 for either kind.
+ * ------------------------------------------------------------------------- */
+#define DD_JPEG_SUB_BITS 1024
+#define DD_JPEG_DECODE_ROUNDS 10
+#define DD_JPEG_EXHAUSTED 1
+#define DD_JPEG_BAD_CODE 2
+#define DD_JPEG_BAD_RUN 4
+#define DD_JPEG_TRAILING 8
+int64_t dd_jpeg_decode_workspace_bytes(int32_t m, int32_t h, int32_t w, int32_t sampling, int64_t max_scan_bytes);
+int dd_jpeg_decode_u8(const uint8_t* scan, int64_t scan_bytes, const int32_t* offsets, const int32_t* lengths,
+                      int64_t max_scan_bytes, const void* tables, int32_t m, int32_t h, int32_t w, int32_t sampling,
+                      uint8_t* out, int32_t* status, void* workspace, int64_t workspace_bytes, int32_t rounds,
+                      dd_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * CLIP text encoder (csrc/clip.hip): the SD-v1.5 `text_encoder` (transformers.CLIPTextModel) that the reference calls at
  * runner/base_runner.py:119,511-514, runner/multiview_runner.py:145,427-428 (`text_encoder(ids)[0]`), through diffusers'
  * _encode_prompt at pipeline/pipeline_bev_controlnet.py:273 and at networks/bbox_embedder.py:133-145
