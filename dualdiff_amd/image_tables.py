@@ -1,7 +1,8 @@
 """Host-side builders of the constants the image and JPEG kernels read, and their device copies.
 
 Pure host code below `ops`: PIL's fixed-point bicubic coefficient tables, torchvision's normalisation table, the JPEG
-header and the encoder's tables.  The `device_*` functions put them on a device under the one rule of `_consts`.
+header and the encoder's tables, and what the PNG encoder builds (it reads no host-built table: its length codes are
+arithmetic, its CRC bitwise).  The `device_*` functions put them on a device under the one rule of `_consts`.
 `pipeline.image_output` re-exports the names for the callers that know them from there.
 """
 import math
@@ -201,3 +202,17 @@ def device_jpeg_tables(h, w, quality, device):
     def build():
         return torch.frombuffer(bytearray(jpeg_header(h, w, quality)), dtype=torch.uint8), jpeg_tables(quality)
     return device_const(("jpeg", int(h), int(w), int(quality)), device, build)
+
+
+# ---- PNG: what is built, and the sizes of its format (csrc/png.hip) ---------------------------------
+
+PNG_MODES = "8-bit RGB (colour type 2), no interlace, no ancillary chunks"
+PNG_CHUNK = 16384                      # filtered bytes per deflate chunk and per IDAT
+PNG_FILE_FIXED = 8 + 25 + 12 + 2 + 4   # signature, IHDR, IEND, the zlib header, the Adler-32
+PNG_CHUNK_FIXED = 12 + 5               # an IDAT's length / type / CRC, a stored block's header
+
+
+def png_capacity(h, w):
+    """The longest file of an (h, w) frame: every chunk stored.  No content makes a file longer."""
+    n = int(h) * (1 + 3 * int(w))
+    return PNG_FILE_FIXED + PNG_CHUNK_FIXED * (-(-n // PNG_CHUNK)) + n

@@ -18,8 +18,8 @@ from ._consts import device_const
 from ._native import DD_BF16, DD_EPI_GEGLU, DD_EPI_NONE, DD_EPI_SILU, DD_F16, AttnDesc, Gemm8Desc, GemmDesc, XAttnDesc
 from ._timer import KernelTimer, _stream, set_timer  # noqa: F401
 from ._workspace import workspace, workspace_owner  # noqa: F401
-from .image_tables import (_image_lut, _image_mean_std, device_jpeg_tables, device_tables,  # noqa: F401
-                           image_norm_lut, jpeg_header)
+from .image_tables import (PNG_FILE_FIXED, _image_lut, _image_mean_std, device_jpeg_tables, device_tables,  # noqa: F401
+                           image_norm_lut, jpeg_header, png_capacity)
 from .tuning import (CHALLENGE_TILES, TUNE_TABLE_PATH, forget_tuned, load_tuned, save_tuned,  # noqa: F401
                      tune_candidates, tuned_table)
 
@@ -524,6 +524,49 @@ def jpeg_encode_u8(frames, quality=75, out=None, capacity=None):
                   # frames read, the int16 coefficients (768 bytes per MCU) written once and read twice; the bit stream is as
                   # long as the content makes it and is not booked
                   book=lambda: ("dd_jpeg_encode", 0.0, float(frames.numel() + 3 * 768 * m * ((h + 15) // 16) * ((w + 15) // 16))))
+    return out, lengths
+
+
+def png_encode_u8(frames, out=None, capacity=None):
+    """uint8 frames (m, H, W, 3) -> one lossless .png file per frame (dd_png_encode_u8): 8-bit RGB, per-row filter choice,
+    one dynamic-Huffman or stored deflate block and one IDAT per 16 KiB of filtered bytes.  -> (buf (m,
+    capacity) uint8, lengths (m,) int32), both on the device: file i is buf[i, :lengths[i]].  capacity defaults to
+    image_tables.png_capacity(H, W), the file with every chunk stored, which no content exceeds; with a smaller one a
+    length above the capacity is the file's true length and the row then holds its first `capacity` bytes.  Nothing is read
+    back and no table comes from the host.  The scratch buffer is ops.workspace's: call once, on the capture stream or
+    under the same workspace_owner, before capturing the launches in a graph."""
+    what = "png_encode_u8"
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
+        raise ValueError("%s takes an (m, H, W, 3) frame batch, got %s" % (what, tuple(frames.shape)))
+    if frames.dtype != torch.uint8:
+        raise ValueError("%s takes uint8 frames, got %s" % (what, frames.dtype))
+    if not frames.is_contiguous():
+        raise ValueError("%s takes a contiguous NHWC tensor" % what)
+    m, h, w = frames.shape[0], frames.shape[1], frames.shape[2]
+    if out is not None:
+        if out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != m or not out.is_contiguous():
+            raise ValueError("%s: out must be a contiguous uint8 (%d, capacity) tensor" % (what, m))
+        if capacity is not None and int(capacity) != out.shape[1]:
+            raise ValueError("%s: capacity %r does not match out %s" % (what, capacity, tuple(out.shape)))
+        capacity = out.shape[1]
+    capacity = png_capacity(h, w) if capacity is None else int(capacity)
+    if capacity < PNG_FILE_FIXED:
+        raise ValueError("%s: capacity must be at least the fixed parts of a file (%d bytes), got %d"
+                         % (what, PNG_FILE_FIXED, capacity))
+    _need_gpu(frames, out)
+    lib = _native.load()
+    need = lib.dd_png_workspace_bytes(m, h, w)
+    if need < 0:
+        raise _native.Unsupported("dualdiff_amd.%s: %d frames of %d x %d are more than one call takes" % (what, m, h, w))
+    if out is None:
+        out = torch.empty((m, capacity), dtype=torch.uint8, device=frames.device)
+    lengths = torch.empty((m,), dtype=torch.int32, device=frames.device)
+    ws = workspace(need, frames.device, kind="png")
+    _timer.launch(what, lib.dd_png_encode_u8, _ptr(frames), m, h, w, _ptr(ws), ws.numel() * 4, _ptr(out), capacity,
+                  _ptr(lengths), _stream(),
+                  # frames read twice by the filter, the filtered bytes written once and read once; the chunks' deflate
+                  # forms are as long as the content makes them and are not booked
+                  book=lambda: ("dd_png_encode", 0.0, float(2 * frames.numel() + 2 * m * h * (1 + 3 * w))))
     return out, lengths
 
 

@@ -24,7 +24,18 @@ tables.  That is integer arithmetic too, and `ops.jpeg_encode_u8` produces the s
     files = encode_jpeg(frames)                           # the 2-level list of `bytes`, one .jpg file each
     save_jpeg(frames, paths)                              # ... written to `paths` (same nesting), directories created
 
-The way back, .jpg files to uint8 frames, is pipeline/jpeg_input.py.  PNG and FID stay with the caller.
+The way back, .jpg files to uint8 frames, is pipeline/jpeg_input.py.
+
+The reference's demo and validation path saves its results as .png instead (tools/test.py:74-97): the 2 x 3 grids of
+the six views that `concat_6_views` builds (runner/img_utils.py:5-40).  PNG is lossless, so the guarantee is not PIL's
+bytes (zlib's match search is one sequential chain) but a valid file that decodes to exactly the frame, encoded on the
+device in a format of independent 16 KiB chunks (`ops.png_encode_u8`):
+
+    grids = concat_views(frames)                          # (b, 2 H, 3 W, 3): views 0-2 over views 3-5
+    files = encode_png(grids)                             # a list of `bytes`, one .png file each
+    save_png(grids, paths)
+
+FID stays with the caller.
 """
 import os
 
@@ -32,7 +43,7 @@ import torch
 
 from .. import ops as O
 from ..image_tables import (JPEG_BASE_CHROMA, JPEG_BASE_LUMA, JPEG_HUFFMAN, JPEG_MODES, JPEG_ZIGZAG,  # noqa: F401
-                            PRECISION_BITS, device_jpeg_tables, device_tables, jpeg_header, jpeg_quant_tables,
+                            PNG_MODES, PRECISION_BITS, device_jpeg_tables, device_tables, jpeg_header, jpeg_quant_tables,
                             jpeg_tables, resample_tables)
 
 INTERPOLATIONS = ("bicubic",)
@@ -147,11 +158,14 @@ def encode_jpeg(u8, quality=75, **options):
 def save_jpeg(u8, paths, quality=75, **options):
     """encode_jpeg, each file written to its path: `paths` nested as the frames are ((b, n) names, or m names).  Missing
     directories are created, as the reference's `mkdir -p` does.  Returns the files' sizes, nested the same way."""
-    files = encode_jpeg(u8, quality, **options)
+    return _save(encode_jpeg(u8, quality, **options), u8, paths, "save_jpeg")
+
+
+def _save(files, u8, paths, what):
     nested = u8.dim() == 5
     rows = list(zip(files, paths)) if nested else [(files, paths)]
     if len(paths) != len(files) or any(len(p) != len(f) for f, p in rows):
-        raise ValueError("save_jpeg takes one path per frame, nested as the frames are")
+        raise ValueError("%s takes one path per frame, nested as the frames are" % what)
     sizes = []
     for fs, ps in rows:
         for data, path in zip(fs, ps):
@@ -162,3 +176,49 @@ def save_jpeg(u8, paths, quality=75, **options):
                 f.write(data)
         sizes.append([len(d) for d in fs])
     return sizes if nested else sizes[0]
+
+
+def _png_options(options):
+    for name, value in options.items():
+        raise ValueError("PNG option %s=%r is not built; available: %s" % (name, value, PNG_MODES))
+
+
+@torch.no_grad()
+def encode_png(u8, **options):
+    """uint8 frames (b, n, H, W, 3) -> the 2-level list of `bytes` (one .png file per frame, nested as encode_jpeg nests
+    its files), (m, H, W, 3) -> a flat list: lossless files that decode to exactly the frames, encoded on the GPU.  One
+    readback of the lengths and one copy of the files' bytes; the default capacity holds any content."""
+    _png_options(options)
+    if u8.dtype != torch.uint8 or u8.dim() not in (4, 5) or u8.shape[-1] != 3 or u8.numel() == 0:
+        raise ValueError("encode_png takes uint8 frames (b, n, H, W, 3) or (m, H, W, 3) (%s), got %s %s"
+                         % (PNG_MODES, tuple(u8.shape), u8.dtype))
+    frames = (u8.flatten(0, 1) if u8.dim() == 5 else u8).contiguous()
+    buf, lengths = O.png_encode_u8(frames)
+    n = lengths.cpu().tolist()
+    raw = buf[:, :max(n)].cpu().numpy()
+    files = [raw[i, :k].tobytes() for i, k in enumerate(n)]
+    if u8.dim() == 4:
+        return files
+    per = u8.shape[1]
+    return [files[i * per:(i + 1) * per] for i in range(u8.shape[0])]
+
+
+def save_png(u8, paths, **options):
+    """encode_png, each file written to its path: `paths` nested as the frames are ((b, n) names, or m names).  Missing
+    directories are created.  Returns the files' sizes, nested the same way."""
+    return _save(encode_png(u8, **options), u8, paths, "save_png")
+
+
+def concat_views(u8, oneline=False):
+    """The reference's `concat_6_views` (runner/img_utils.py:5-40) for equal-sized views, on the tensor's device: frames
+    (b, 6, H, W, 3) -> (b, 2 H, 3 W, 3), views 0-2 over views 3-5; oneline=True: (b, n, H, W, 3), n >= 2 -> (b, H, n W, 3)."""
+    if u8.dim() != 5 or u8.shape[-1] != 3:
+        raise ValueError("concat_views takes frames (b, n, H, W, 3), got %s" % (tuple(u8.shape),))
+    b, n, h, w, _ = u8.shape
+    if oneline:
+        if n < 2:
+            raise ValueError("concat_views(oneline=True) takes at least 2 views, got %d" % n)
+        return u8.permute(0, 2, 1, 3, 4).reshape(b, h, n * w, 3)
+    if n != 6:
+        raise ValueError("concat_views takes 6 views for the 2 x 3 grid, got %d (oneline=True takes any n >= 2)" % n)
+    return u8.reshape(b, 2, 3, h, w, 3).permute(0, 1, 3, 2, 4, 5).reshape(b, 2 * h, 3 * w, 3)

@@ -572,6 +572,28 @@ int dd_jpeg_encode_u8(const uint8_t* frames, int32_t m, int32_t h, int32_t w, co
                       int32_t* lengths, dd_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * PNG output (csrc/png.hip): the same uint8 frames -> lossless .png files, as the reference's demo and validation path
+ * saves its view grids (tools/test.py:74-97, runner/img_utils.py:5-40).  Not PIL's bytes (zlib's lazy-match parse is one
+ * sequential chain): a valid PNG that decodes to exactly the input, in a format fixed so that every step is local to a
+ * row, a run of equal bytes or a 16 KiB chunk: 8-bit RGB, colour type 2, no interlace; per row the
+ * filter 0..4 with the smallest sum of min(b, 256 - b), ties to the lowest type; the filtered stream in chunks of 16384
+ * bytes, each one dynamic-Huffman block over literals and distance-1 matches (zlib Z_RLE's rule) that an empty stored
+ * block aligns, or one stored block where that is shorter; one IDAT per chunk.
+ *
+ * frames: uint8 [m][h][w][3] (device), any alignment.  out: uint8 [m][capacity], row i = file i; lengths: int32 [m], the
+ * TRUE length of file i also when it exceeds capacity — the row then holds the first `capacity` bytes of the file and
+ * nothing is written outside it.  No file is longer than 51 + 17 * ceil(n / 16384) + n bytes, n = h * (1 + 3 * w).
+ * workspace: at least dd_png_workspace_bytes(m, h, w) bytes, 16-byte aligned, contents don't care before and after.
+ * Four launches on `stream` whatever m and the content are, no host synchronisation: the call can be captured in a graph.
+ * DD_ERR_BAD_ARG, before any runtime call: a NULL pointer, m / h / w <= 0, capacity < 51 (signature, IHDR, IEND, the zlib
+ * header and the Adler-32), a misaligned workspace / lengths, workspace_bytes too small.  m > 65535 or a frame whose
+ * longest possible file exceeds 2^31 - 1 bytes: DD_ERR_UNSUPPORTED; dd_png_workspace_bytes returns -1 for either kind.
+ * ------------------------------------------------------------------------- */
+int64_t dd_png_workspace_bytes(int32_t m, int32_t h, int32_t w);
+int dd_png_encode_u8(const uint8_t* frames, int32_t m, int32_t h, int32_t w, void* workspace, int64_t workspace_bytes,
+                     uint8_t* out, int64_t capacity, int32_t* lengths, dd_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * JPEG input (csrc/jpeg_decode.hip, csrc/jpeg_decode_core.h): the entropy-coded segments of m baseline .jpg files of one
  * geometry -> uint8 frames [m][h][w][3] (device), byte for byte what PIL's `Image.open(f).convert("RGB")` returns for
  * the camera files the reference opens (configs/dataset/Nuscenes.yaml:98,183 LoadMultiViewImageFromFiles,
