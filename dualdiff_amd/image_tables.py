@@ -212,6 +212,12 @@ PNG_FILE_FIXED = 8 + 25 + 12 + 2 + 4   # signature, IHDR, IEND, the zlib header,
 PNG_CHUNK_FIXED = 12 + 5               # an IDAT's length / type / CRC, a stored block's header
 
 
+def png_unit_lut():
+    """torchvision's ToTensor on every byte value, with torch's own float32 division: (256,) float32 on the host,
+    lut[b] = float32(b) / 255 — what the image-mode ORS condition is made of (ops.png_condition)."""
+    return torch.arange(256).float().div(255).contiguous()
+
+
 def png_capacity(h, w):
     """The longest file of an (h, w) frame: every chunk stored.  No content makes a file longer."""
     n = int(h) * (1 + 3 * int(w))

@@ -19,7 +19,7 @@ from ._native import DD_BF16, DD_EPI_GEGLU, DD_EPI_NONE, DD_EPI_SILU, DD_F16, At
 from ._timer import KernelTimer, _stream, set_timer  # noqa: F401
 from ._workspace import workspace, workspace_owner  # noqa: F401
 from .image_tables import (PNG_FILE_FIXED, _image_lut, _image_mean_std, device_jpeg_tables, device_tables,  # noqa: F401
-                           image_norm_lut, jpeg_header, png_capacity)
+                           image_norm_lut, jpeg_header, png_capacity, png_unit_lut)
 from .tuning import (CHALLENGE_TILES, TUNE_TABLE_PATH, forget_tuned, load_tuned, save_tuned,  # noqa: F401
                      tune_candidates, tuned_table)
 
@@ -624,6 +624,102 @@ def jpeg_decode_u8(scan, offsets, lengths, tables, h, w, sampling, max_scan_byte
                   # the content makes them read and are not booked
                   book=lambda: ("dd_jpeg_decode", 0.0, float(3 * scan.numel() + out.numel())))
     return out, status
+
+
+PNG_DECODE_COLOUR_TYPES = (0, 2, 6)  # grey, RGB, RGBA at bit depth 8
+PNG_DECODE_CHUNK = 16384            # filtered bytes per IDAT of png_encode_u8's own files (csrc/png.hip)
+PNG_DECODE_STATUS = ((1, "the stream ends inside a block or before the Adler-32"), (2, "a reserved block type"),
+                     (4, "a stored block whose LEN is not the complement of NLEN"), (8, "bad code lengths"),
+                     (16, "an invalid symbol"), (32, "a distance before the start of the output"),
+                     (64, "more bytes than the frame"), (128, "fewer bytes than the frame"), (256, "the Adler-32 does not match"),
+                     (512, "a bad zlib header"), (1024, "a bad filter type"))
+
+
+def png_decode_u8(streams, files, tab, colour_types, h, w, chunked=None, out=None):
+    """The concatenated IDAT payloads of m .png files of one geometry -> (frames (m, h, w, 3) uint8, status (m,) int32,
+    paths (m,) int32), all on the device, the frames byte for byte PIL's `Image.open(f).convert("RGB")`
+    (dd_png_decode_u8).  streams: uint8 (n,); files: int32 (m, 4), per file the stream's offset and length, the colour
+    type and the index in `tab` of its IDAT boundaries or -1; tab: int32 (k,) or None — device tensors, usually views of
+    one upload (pipeline/png_input.py: upload_png).  colour_types: the m colour types as Python ints (the host knows them;
+    nothing is read back).  chunked: None to decode the files whose entry names a place in `tab` chunk by chunk where
+    the device can verify that this is the sequential decode, False to send every file through the sequential path; the
+    frames do not depend on it.  status[i] is 0 or one of PNG_DECODE_STATUS's bits; a bad frame leaves the others alone.
+    paths[i] is 1 where the chunk-parallel result was used.  The scratch buffer is ops.workspace's: call once before
+    capturing the launches in a graph."""
+    what = "png_decode_u8"
+    if streams.dtype != torch.uint8 or streams.dim() != 1 or streams.numel() == 0 or not streams.is_contiguous():
+        raise ValueError("%s takes the streams as a contiguous uint8 (n,) tensor, got %s %s" % (what, tuple(streams.shape), streams.dtype))
+    if files.dtype != torch.int32 or files.dim() != 2 or files.shape[1] != 4 or files.shape[0] == 0 or not files.is_contiguous():
+        raise ValueError("%s: files must be a contiguous int32 (m, 4) tensor, got %s %s" % (what, tuple(files.shape), files.dtype))
+    m = files.shape[0]
+    if tab is not None and (tab.dtype != torch.int32 or tab.dim() != 1 or not tab.is_contiguous()):
+        raise ValueError("%s: tab must be a contiguous int32 (k,) tensor or None, got %s %s" % (what, tuple(tab.shape), tab.dtype))
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in (h, w)):
+        raise ValueError("%s: h and w are ints" % what)
+    if h <= 0 or w <= 0:
+        raise ValueError("%s: a frame is at least 1 x 1, got %d x %d" % (what, h, w))
+    colour_types = [int(c) for c in colour_types]
+    if len(colour_types) != m or any(c not in PNG_DECODE_COLOUR_TYPES for c in colour_types):
+        raise ValueError("%s: colour_types must be %d of %s, got %r" % (what, m, PNG_DECODE_COLOUR_TYPES, colour_types))
+    if chunked not in (None, False):
+        raise ValueError("%s: chunked is None (verify and use the chunks) or False (the sequential path), got %r" % (what, chunked))
+    out = _image_out(out, (m, h, w, 3), streams.device, what)
+    _need_gpu(streams, files, tab, out)
+    if files.data_ptr() % 4 or (tab is not None and tab.data_ptr() % 4):
+        raise ValueError("%s: files and tab must start on a 4-byte boundary" % what)
+    status = torch.empty((m,), dtype=torch.int32, device=streams.device)
+    paths = torch.empty((m,), dtype=torch.int32, device=streams.device)
+    lib = _native.load()
+    need = lib.dd_png_decode_workspace_bytes(m, h, w)
+    if need < 0:
+        raise _native.Unsupported("dualdiff_amd.%s: %d frames of %d x %d are more than one call takes" % (what, m, h, w))
+    ws = workspace(need, streams.device, kind="png_decode")
+    ntab = 0 if tab is None else tab.numel()
+    types = (ctypes.c_int32 * m)(*colour_types)
+    _timer.launch(what, lib.dd_png_decode_u8, _ptr(streams), streams.numel(), _ptr(files), _ptr(tab) if ntab else None, ntab,
+                  types, m, h, w, 1 if chunked is None else 0, _ptr(out), _ptr(status), _ptr(paths), _ptr(ws),
+                  ws.numel() * 4, _stream(),
+                  # the streams read once; the filtered bytes written, summed, unfiltered in place and read once more; the
+                  # frames written
+                  book=lambda: ("dd_png_decode", 0.0, float(streams.numel() + 5 * m * h * (1 + 4 * w) + out.numel())))
+    return out, status, paths
+
+
+def png_condition(frames, views=6, top=0, left=0, size=None, out=None):
+    """uint8 frames (b, H, W, 3), each a panorama of `views` views side by side -> float32 (b, 3, oh, views * ow), NCHW:
+    `ToTensor()` of rows top .. top + oh and, per view, columns left .. left + ow (dd_png_condition; dataset/utils.py:
+    348-408).  size: (oh, ow), None for the rest of the view.  The value of a byte is float32(byte) / 255 from a table
+    built on the host (image_tables.png_unit_lut), a device constant under the rule of _consts."""
+    what = "png_condition"
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
+        raise ValueError("%s takes a (b, H, W, 3) frame batch, got %s" % (what, tuple(frames.shape)))
+    if frames.dtype != torch.uint8:
+        raise ValueError("%s takes uint8 frames, got %s" % (what, frames.dtype))
+    if not frames.is_contiguous():
+        raise ValueError("%s takes a contiguous NHWC tensor" % what)
+    b, h, w = frames.shape[0], frames.shape[1], frames.shape[2]
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in (views, top, left)) or views <= 0 or w % views:
+        raise ValueError("%s: views must be a positive int that divides the width %d, top and left ints; got %r, %r, %r"
+                         % (what, w, views, top, left))
+    pw = w // views
+    try:
+        oh, ow = (h - top, pw - left) if size is None else (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError("size must be (h, w), got %r" % (size,))
+    if not (0 <= top and 0 <= left and 0 < oh and 0 < ow and top + oh <= h and left + ow <= pw):
+        raise ValueError("%s: the crop top %d, left %d, size %d x %d leaves the %d x %d view" % (what, top, left, oh, ow, h, pw))
+    shape = (b, 3, oh, views * ow)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=frames.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError("%s: out must be a contiguous float32 %s tensor" % (what, shape))
+    _need_gpu(frames, out)
+    _forget_derived(out)
+    lib = _native.load()
+    lut = device_const("png_unit_lut", frames.device, png_unit_lut)
+    _timer.launch(what, lib.dd_png_condition, _ptr(frames), _ptr(out), _ptr(lut), b, h, w, views, top, left, oh, ow, _stream(),
+                  book=lambda: ("dd_png_condition_kernel", 0.0, float(out.numel() * 5)))
+    return out
 
 
 BOX_POINT_MODES = {"all-xyz": 0, "cxyz": 1}      # dataset/utils.py:222-226; points per box 8 / 4

@@ -646,6 +646,64 @@ int dd_jpeg_decode_u8(const uint8_t* scan, int64_t scan_bytes, const int32_t* of
                       dd_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * PNG input (csrc/png_decode.hip, csrc/png_decode_core.h): the IDAT payloads of m .png files of one geometry -> uint8
+ * frames [m][h][w][3] (device), byte for byte what PIL's `Image.open(f).convert("RGB")` returns: the files of the
+ * reference's default ORS condition, one RGBA panorama of six views per sample (magicdrive/dataset/dataset_wrapper.py:62-81
+ * OccFolderSetWrapper(mode='image'), misc/test_utils.py:218-222), and the files dd_png_encode_u8 writes
+ * (tools/test.py:74-97).  Bit depth 8, no interlace, colour type 0 (grey, replicated), 2 (RGB) or 6 (RGBA, alpha
+ * dropped); any zlib stream: stored, fixed and dynamic blocks, distances up to 32768, any number of blocks.  The host walks
+ * the chunks and checks their CRCs (pipeline/png_input.py: parse_png); inflate, the Adler-32, the five row filters and
+ * the conversion run on the device.
+ *
+ * streams: streams_bytes bytes (device) that hold every file's concatenated IDAT payloads, chunk framing stripped.
+ * files: int32 [m][4] (device): the stream's offset in `streams`, its length, the file's colour type, and the index in
+ * `tab` of the file's IDAT boundaries or -1.  Every read is clamped to the stream and to [0, streams_bytes), whatever the
+ * tables hold.  tab: int32 [ntab] (device, may be NULL when ntab is 0): for a file that has the shape of
+ * dd_png_encode_u8's format — colour type 2, exactly ceil(h (1 + 3 w) / 16384) IDATs — its n + 1 IDAT boundaries relative
+ * to the stream's start.  The shape proves nothing, so the device verifies: one workgroup per IDAT inflates it from bit 0
+ * into its 16 KiB slot, and the file counts as chunked only if every one consumed exactly its payload, produced exactly
+ * its slot, reached with no match before its slot and met BFINAL exactly at the end of the last one — then the result is
+ * the sequential decode's, by induction over the chunks.  Any other file is inflated by one workgroup from its first
+ * block to its last, in the launch behind, with no host synchronisation between the two.
+ * colour_types: int32 [m] in HOST memory, read before the launches: the same colour types, for validation.
+ * chunked: 1 to use `tab`, 0 to send every file through the sequential path (the frames do not depend on it).
+ * out: uint8 [m][h][w][3].  status: int32 [m], per frame 0 or one of the DD_PNG_* bits below — the first thing found
+ * wrong; the frame's pixels are then unspecified, the other frames' are not affected.  paths: int32 [m], 1 where the
+ * chunk-parallel result was used.  workspace: at least dd_png_decode_workspace_bytes(m, h, w) bytes, 16-byte aligned.
+ * One memset and four launches on `stream` (three with chunked 0 or ntab 0) whatever m and the content are; every loop
+ * of the kernels consumes input bits or counts against the frame's size, every read is bounded by the stream and every
+ * write by the frame, so a broken file costs its own frame and nothing else.  No host synchronisation: the call can be
+ * captured in a graph.
+ * DD_ERR_BAD_ARG, before any runtime call: a NULL pointer, m / h / w / streams_bytes <= 0, ntab < 0, chunked not 0 / 1,
+ * a colour type other than 0 / 2 / 6, a misaligned workspace / files / tab / status / paths, workspace_bytes too small.
+ * m > 65535 or a frame of more than 2^31 - 16385 filtered bytes at four bytes per pixel: DD_ERR_UNSUPPORTED;
+ * dd_png_decode_workspace_bytes returns -1 for either kind.
+ *
+ * dd_png_condition: the collate step of that condition (dataset/utils.py:348-408), one launch: uint8 frames [b][h][w][3],
+ * each a panorama of `views` views side by side, -> float32 [b][3][oh][views * ow], the `ToTensor()` value lut[byte] of
+ * rows top .. top + oh and, per view, columns left .. left + ow (crop_hd: top 176, left 32, 256 x 704 of 432 x 768).
+ * lut: float32 [256] (device): byte / 255, built by the caller.  DD_ERR_BAD_ARG: a NULL pointer, a size <= 0, top or
+ * left < 0, w no multiple of views, a crop that leaves the view, a misaligned out / lut.
+ * ------------------------------------------------------------------------- */
+#define DD_PNG_TRUNCATED 1
+#define DD_PNG_BAD_BLOCK 2
+#define DD_PNG_BAD_STORED 4
+#define DD_PNG_BAD_LENGTHS 8
+#define DD_PNG_BAD_SYMBOL 16
+#define DD_PNG_BAD_DISTANCE 32
+#define DD_PNG_TOO_LONG 64
+#define DD_PNG_TOO_SHORT 128
+#define DD_PNG_BAD_ADLER 256
+#define DD_PNG_BAD_ZLIB 512
+#define DD_PNG_BAD_FILTER 1024
+int64_t dd_png_decode_workspace_bytes(int32_t m, int32_t h, int32_t w);
+int dd_png_decode_u8(const uint8_t* streams, int64_t streams_bytes, const int32_t* files, const int32_t* tab, int32_t ntab,
+                     const int32_t* colour_types, int32_t m, int32_t h, int32_t w, int32_t chunked, uint8_t* out,
+                     int32_t* status, int32_t* paths, void* workspace, int64_t workspace_bytes, dd_stream_t stream);
+int dd_png_condition(const uint8_t* frames, float* out, const float* lut, int32_t b, int32_t h, int32_t w, int32_t views,
+                     int32_t top, int32_t left, int32_t oh, int32_t ow, dd_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * CLIP text encoder (csrc/clip.hip): the SD-v1.5 `text_encoder` (transformers.CLIPTextModel) that the reference calls at
  * runner/base_runner.py:119,511-514, runner/multiview_runner.py:145,427-428 (`text_encoder(ids)[0]`), through diffusers'
  * _encode_prompt at pipeline/pipeline_bev_controlnet.py:273 and at networks/bbox_embedder.py:133-145
