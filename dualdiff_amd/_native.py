@@ -174,6 +174,10 @@ SIGNATURES = {
                                    c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "dd_png_condition": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                    c_int32, c_int32, c_void_p]),
+    "dd_map_render_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                   c_int32, c_void_p]),
+    "dd_map_compose_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                    c_int32, c_void_p]),
     "dd_clip_embed": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                 c_int32, c_int32, c_void_p]),
     "dd_causal_attention": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,

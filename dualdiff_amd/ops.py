@@ -790,6 +790,81 @@ def box_views(corners, labels, offsets, transforms, views, cap, points_mode="all
     return out
 
 
+MAP_MAX_LAYERS = 31                              # include/dualdiff_hip.h: DD_MAP_MAX_LAYERS; bit 31 of `used` is taken
+MAP_SIDES = {"right": 0, "below": 1}
+
+
+def map_render_u8(maps, stab, dtab, ns, nd):
+    """The layers of a batch of BEV maps -> the coloured maps and the classes in use, in one launch (include/
+    dualdiff_hip.h: dd_map_render_u8; runner/map_visualizer.py:106-132, 180-190).  maps (b, C, S, S) uint8 holding 0 / 1,
+    stab (ns + 1, 4) fp32 = colour / 255 and priority rank per static layer plus the "nothing" row, dtab (nd, 4) fp32 =
+    colour / 255 per dynamic layer or None for nd == 0; ns + nd <= C — all contiguous device tensors.
+    -> (img (b, 3, S, S) fp32 holding colour / 255: what image_resample_u8 quantises back to the colour bytes, used (b,)
+    int32).  Nothing is read back."""
+    what = "map_render_u8"
+    if maps.dim() != 4 or maps.shape[2] != maps.shape[3] or maps.numel() == 0:
+        raise ValueError("%s takes square maps (b, C, S, S), got %s" % (what, tuple(maps.shape)))
+    if maps.dtype != torch.uint8:
+        raise ValueError("%s takes uint8 maps, got %s" % (what, maps.dtype))
+    b, c, s = maps.shape[0], maps.shape[1], maps.shape[2]
+    ns, nd = int(ns), int(nd)
+    if ns < 0 or nd < 0 or ns + nd == 0 or ns + nd > c:
+        raise ValueError("%s: %d static + %d dynamic layers do not fit a map of %d layers" % (what, ns, nd, c))
+    if ns + nd > MAP_MAX_LAYERS:
+        raise ValueError("%s: at most %d layers, got %d + %d" % (what, MAP_MAX_LAYERS, ns, nd))
+    if stab.dtype != torch.float32 or tuple(stab.shape) != (ns + 1, 4):
+        raise ValueError("%s: stab must be fp32 (%d, 4), got %s %s" % (what, ns + 1, stab.dtype, tuple(stab.shape)))
+    if nd > 0 and (dtab is None or dtab.dtype != torch.float32 or tuple(dtab.shape) != (nd, 4)):
+        raise ValueError("%s: dtab must be fp32 (%d, 4)" % (what, nd))
+    ins = (maps, stab, dtab if nd > 0 else None)
+    if any(t is not None and not t.is_contiguous() for t in ins):
+        raise ValueError("%s takes contiguous tensors" % what)
+    _need_gpu(*ins)
+    img = torch.empty((b, 3, s, s), dtype=torch.float32, device=maps.device)
+    used = torch.empty((b,), dtype=torch.int32, device=maps.device)
+    lib = _native.load()
+    _timer.launch(what, lib.dd_map_render_u8, _ptr(maps), _ptr(stab), _ptr(ins[2]), _ptr(img), _ptr(used), b, c, s, ns, nd,
+                  _stream(), book=lambda: ("dd_map_render_kernel", 0.0, float(b * s * s * (ns + nd + 12))))
+    return img, used
+
+
+def map_compose_u8(src, index=None, legend=None, side="right"):
+    """The quarter turn, the zero pad and the legend of `visualize_map` (runner/map_visualizer.py:197-209) for the samples
+    of a batch that share a legend, in one launch (dd_map_compose_u8).  src (m, T, T, 3) uint8: the resized, not yet turned
+    pictures; index (g,) int32: the samples to take, None for all of them in order; legend (lh, lw, 3) uint8 or None;
+    side "right" (lh <= T) or "below" (lw <= T) — contiguous device tensors.
+    -> (g, T, T + lw, 3) or (g, T + lh, T, 3) uint8: np.rot90 of the picture, the legend beside or below it, zero elsewhere."""
+    what = "map_compose_u8"
+    if src.dim() != 4 or src.shape[1] != src.shape[2] or src.shape[3] != 3 or src.numel() == 0 or src.dtype != torch.uint8:
+        raise ValueError("%s takes square uint8 pictures (m, T, T, 3), got %s %s" % (what, src.dtype, tuple(src.shape)))
+    if side not in MAP_SIDES:
+        raise ValueError("%s: side must be one of %s, got %r" % (what, ", ".join(sorted(MAP_SIDES)), side))
+    m, t = src.shape[0], src.shape[1]
+    g = m
+    if index is not None:
+        if index.dtype != torch.int32 or index.dim() != 1 or index.numel() == 0:
+            raise ValueError("%s: index must be a non-empty int32 vector, got %s %s" % (what, index.dtype, tuple(index.shape)))
+        g = index.shape[0]
+    lh = lw = 0
+    if legend is not None:
+        if legend.dim() != 3 or legend.shape[2] != 3 or legend.numel() == 0 or legend.dtype != torch.uint8:
+            raise ValueError("%s: legend must be uint8 (lh, lw, 3), got %s %s" % (what, legend.dtype, tuple(legend.shape)))
+        lh, lw = legend.shape[0], legend.shape[1]
+        if (lh if side == "right" else lw) > t:
+            raise ValueError("%s: a %d x %d legend does not lie %s a %d x %d picture" % (what, lh, lw, side, t, t))
+    ins = (src, index, legend)
+    if any(x is not None and not x.is_contiguous() for x in ins):
+        raise ValueError("%s takes contiguous tensors" % what)
+    _need_gpu(*ins)
+    shape = (g, t, t + lw, 3) if side == "right" else (g, t + lh, t, 3)
+    out = torch.empty(shape, dtype=torch.uint8, device=src.device)
+    lib = _native.load()
+    _timer.launch(what, lib.dd_map_compose_u8, _ptr(src), _ptr(index), _ptr(legend), _ptr(out), m, g, t, lh, lw,
+                  MAP_SIDES[side], _stream(),
+                  book=lambda: ("dd_map_compose_kernel", 0.0, float(g * t * t * 3 + out.numel())))
+    return out
+
+
 def groupnorm(x, gamma, beta, m, hw, groups, eps, silu, x2=None, out=None):
     """GroupNorm (+SiLU) over an NHWC batch; x2 = optional second source concatenated on C."""
     lib = _native.load()

@@ -704,6 +704,45 @@ int dd_png_condition(const uint8_t* frames, float* out, const float* lut, int32_
                      int32_t top, int32_t left, int32_t oh, int32_t ow, dd_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Map output (csrc/map.hip): the picture the reference's `visualize_map` makes of a sample's BEV map
+ * (runner/map_visualizer.py:143-211; misc/test_utils.py:344-348 calls it per sample, tools/test.py:76 saves it).
+ *
+ * dd_map_render_u8: the colouring (:106-132, :180-190) and the classes in use (:114-115, :127-128), one launch.
+ *   maps  uint8 [b][c][s][s] (device), 0 / 1: static layers are planes [0, ns), dynamic layers [ns, ns + nd); planes from
+ *         ns + nd on are not read.  ns + nd <= c.
+ *   stab  float [ns + 1][4] (device): per static layer {r / 255, g / 255, b / 255, rank}, rank = its index in the
+ *         reference's STATIC_PRIORITY (:49-60); row ns is the "nothing" colour (:43), whose rank is not read.
+ *   dtab  float [nd][4] (device): per dynamic layer its colour / 255; NULL when nd == 0.
+ *   img   float [b][3][s][s]: per pixel the colour / 255 of the first set dynamic layer (argmax, :127-130), else of the set
+ *         static layer of the greatest rank (:67-73; the first one among equal ranks), else of "nothing".  The quotients
+ *         are the caller's, so that dd_image_resample_u8 quantises them back to the colour bytes.
+ *   used  int32 [b]: whatever it held before, bit k < ns: static layer k is set at some pixel; bit ns + j: dynamic layer j
+ *         is the argmax at some pixel, which for j = 0 includes every pixel with no dynamic layer set; bit 31: some read
+ *         byte is neither 0 nor 1 (the picture is then unspecified).  Cleared on the stream, then one vector atomic OR
+ *         per workgroup.
+ * DD_ERR_BAD_ARG, before any runtime call: a NULL maps / stab / img / used, NULL dtab with nd > 0, b / c / s <= 0, ns or
+ * nd < 0, ns + nd == 0 or > c, a table, img or used that is not 4-byte aligned.  ns + nd > DD_MAP_MAX_LAYERS (bit 31 is
+ * taken), s >= 2^14 or b > 65535: DD_ERR_UNSUPPORTED.
+ *
+ * dd_map_compose_u8: what follows the resize (:197-209) for g samples that share a legend, one launch.
+ *   src    uint8 [m][t][t][3] (device): the resized, not yet turned pictures (dd_image_resample_u8's output);
+ *   index  int32 [g] (device): the sample of src each output takes, clamped to [0, m); NULL: g == m, in order;
+ *   legend uint8 [lh][lw][3] (device), or NULL with lh == lw == 0;
+ *   side   0: the legend to the right (the reference's choice for lh > lw), out [g][t][t + lw][3], lh <= t;
+ *          1: below, out [g][t + lh][t][3], lw <= t.
+ *   out[r][c] = src[c][t - 1 - r] for r, c < t: Image.rotate(90) of a square image, i.e. np.rot90(x, 1); the legend at
+ *   (0, t) or (t, 0); zero elsewhere, as np.pad leaves it.
+ * DD_ERR_BAD_ARG, before any runtime call: a NULL src / out, m / g / t <= 0, lh or lw < 0, a legend without a size or a
+ * size without a legend, side not 0 / 1, NULL index with g != m, a misaligned index, a legend longer than the side it
+ * lies along.  t, lh or lw >= 2^14, m or g > 65535: DD_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------- */
+#define DD_MAP_MAX_LAYERS 31
+int dd_map_render_u8(const uint8_t* maps, const float* stab, const float* dtab, float* img, int32_t* used, int32_t b,
+                     int32_t c, int32_t s, int32_t ns, int32_t nd, dd_stream_t stream);
+int dd_map_compose_u8(const uint8_t* src, const int32_t* index, const uint8_t* legend, uint8_t* out, int32_t m, int32_t g,
+                      int32_t t, int32_t lh, int32_t lw, int32_t side, dd_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * CLIP text encoder (csrc/clip.hip): the SD-v1.5 `text_encoder` (transformers.CLIPTextModel) that the reference calls at
  * runner/base_runner.py:119,511-514, runner/multiview_runner.py:145,427-428 (`text_encoder(ids)[0]`), through diffusers'
  * _encode_prompt at pipeline/pipeline_bev_controlnet.py:273 and at networks/bbox_embedder.py:133-145
