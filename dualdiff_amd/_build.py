@@ -19,7 +19,7 @@ GEMM_SOURCES = ["gemm23.hip", "gemm2_conv.hip", "gemm2_upfold.hip", "gemm1.hip",
 # Longest compile first, so that the pool does not end on one long unit: gemm23 30 s, gemm2_conv and attention 20 s, gemm1
 # and conv3s 16 s, gemm2_upfold 14 s, every other one under 10 s.
 SOURCES = ["gemm23.hip", "gemm2_conv.hip", "attention.hip", "gemm1.hip", "conv3s.hip", "gemm2_upfold.hip", "gemm2_geglu.hip", "gemm4.hip",
-           "norm.hip", "elementwise.hip", "tokens.hip", "xattn.hip", "clip.hip", "gemm8.hip", "vae.hip", "image.hip", "boxes.hip", "jpeg.hip", "jpeg_decode.hip", "png.hip", "png_decode.hip", "map.hip", "gemm.hip"]
+           "norm.hip", "elementwise.hip", "tokens.hip", "xattn.hip", "clip.hip", "gemm8.hip", "vae.hip", "image.hip", "boxes.hip", "jpeg.hip", "jpeg_decode.hip", "png.hip", "png_decode.hip", "map.hip", "box_overlay.hip", "gemm.hip"]
 # per-source extra flags: the attention softmax lives on the MFMA results, so ask LLVM for the
 # VGPR-destination form of MFMA (gfx950 has a unified register file) instead of AGPR accumulators
 # that cost a v_accvgpr_read/write per touched element.

@@ -169,6 +169,9 @@ SIGNATURES = {
     "dd_png_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "dd_png_encode_u8": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                    c_void_p]),
+    "dd_png_workspace_bytes_c": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "dd_png_encode_u8c": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64,
+                                    c_void_p, c_void_p]),
     "dd_png_decode_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "dd_png_decode_u8": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32,
                                    c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -178,6 +181,10 @@ SIGNATURES = {
                                    c_int32, c_void_p]),
     "dd_map_compose_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                     c_int32, c_void_p]),
+    "dd_box_edges": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dd_box_draw_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                 c_int32, c_int32, c_int32, c_void_p]),
     "dd_clip_embed": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                 c_int32, c_int32, c_void_p]),
     "dd_causal_attention": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,

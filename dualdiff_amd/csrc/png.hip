@@ -1,11 +1,12 @@
-// PNG output: uint8 frames (m, H, W, 3) in device memory -> lossless .png files, one per frame.
+// PNG output: uint8 frames (m, H, W, 3) — or (m, H, W, 4), RGBA: dd_png_encode_u8c — in device memory -> lossless .png
+// files, one per frame.
 //
 // The reference's demo and validation path saves every result as .png (tools/test.py:74-97: `{n}_gen{ti}.png`,
 // `{n}_ori.png`, `{n}_map.png`, the view grids of runner/img_utils.py:5-40).  PIL's bytes are zlib's lazy-match parse, one
 // sequential chain, and are not reproduced.  What is produced is a valid PNG that decodes to exactly the input pixels, in a
 // format every step of which is local to a row, to a run of equal bytes or to a 16 KiB chunk:
 //
-//   signature, IHDR (W, H, depth 8, colour type 2, no interlace), one IDAT per chunk, IEND;
+//   signature, IHDR (W, H, depth 8, colour type 2 — 6 for RGBA —, no interlace), one IDAT per chunk, IEND;
 //   the IDAT payloads concatenate to one zlib stream: 78 01, one deflate block (pair) per chunk, the Adler-32;
 //   per row the filter type 0..4 with the smallest sum of min(b, 256 - b) over its filtered bytes, ties to the lowest type;
 //   the filtered stream cut into chunks of 16384 bytes; per chunk literals and distance-1 matches of length 3..258 by
@@ -85,7 +86,8 @@ __device__ const uint8_t kClOrder[kCl] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 
 
 struct Geom {
   int32_t h, w;
-  int32_t row;                                 // filtered bytes per row: 1 + 3 w
+  int32_t bpp;                                 // bytes per pixel: 3 (RGB, colour type 2) or 4 (RGBA, colour type 6)
+  int32_t row;                                 // filtered bytes per row: 1 + bpp w
   int32_t nchunk;                              // chunks per frame
   int64_t len;                                 // filtered bytes per frame
   int64_t stride;                              // ... rounded up to 16: a frame's place in the workspace
@@ -101,10 +103,10 @@ struct Layout {
 static inline int64_t up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 // false: the frame's worst-case file does not fit the int32 lengths
-static inline bool geometry(int32_t m, int32_t h, int32_t w, Geom* g, Layout* l) {
-  const int64_t row = 1 + 3 * (int64_t)w, len = row * h, nchunk = (len + kChunk - 1) / kChunk;
+static inline bool geometry(int32_t m, int32_t h, int32_t w, int32_t bpp, Geom* g, Layout* l) {
+  const int64_t row = 1 + bpp * (int64_t)w, len = row * h, nchunk = (len + kChunk - 1) / kChunk;
   if (kFileFixed + kChunkFixed * nchunk + len > 0x7fffffff) return false;
-  g->h = h; g->w = w; g->row = (int32_t)row; g->nchunk = (int32_t)nchunk; g->len = len; g->stride = up16(len);
+  g->h = h; g->w = w; g->bpp = bpp; g->row = (int32_t)row; g->nchunk = (int32_t)nchunk; g->len = len; g->stride = up16(len);
   int64_t at = 0;
   l->filt = at; at += (int64_t)m * g->stride;
   l->slot = at; at += (int64_t)m * nchunk * kSlot;
@@ -150,12 +152,12 @@ void dd_png_filter_kernel(const uint8_t* __restrict__ frames, uint8_t* __restric
   const int tid = threadIdx.x;
   const int y = blockIdx.x;
   const int64_t img = blockIdx.y;
-  const int nb = 3 * g.w;
+  const int nb = g.bpp * g.w, bpp = g.bpp;
   const uint8_t* cur = frames + (img * g.h + y) * (int64_t)nb;
   const uint8_t* up = cur - nb;                              // read for y > 0 only
   uint32_t sums[5] = {0u, 0u, 0u, 0u, 0u};
   for (int k = tid; k < nb; k += kThreads) {
-    const int x = cur[k], a = k >= 3 ? cur[k - 3] : 0, b = y > 0 ? up[k] : 0, c = (y > 0 && k >= 3) ? up[k - 3] : 0;
+    const int x = cur[k], a = k >= bpp ? cur[k - bpp] : 0, b = y > 0 ? up[k] : 0, c = (y > 0 && k >= bpp) ? up[k - bpp] : 0;
 #pragma unroll
     for (int t = 0; t < 5; ++t) {
       const uint32_t v = dd_png_filter(t, x, a, b, c);
@@ -175,7 +177,7 @@ void dd_png_filter_kernel(const uint8_t* __restrict__ frames, uint8_t* __restric
   uint8_t* dst = filt + img * g.stride + (int64_t)y * g.row;
   if (tid == 0) dst[0] = (uint8_t)type;
   for (int k = tid; k < nb; k += kThreads) {
-    const int x = cur[k], a = k >= 3 ? cur[k - 3] : 0, b = y > 0 ? up[k] : 0, c = (y > 0 && k >= 3) ? up[k - 3] : 0;
+    const int x = cur[k], a = k >= bpp ? cur[k - bpp] : 0, b = y > 0 ? up[k] : 0, c = (y > 0 && k >= bpp) ? up[k - bpp] : 0;
     dst[1 + k] = (uint8_t)dd_png_filter(type, x, a, b, c);
   }
 }
@@ -597,7 +599,7 @@ void dd_png_assemble_kernel(const uint8_t* __restrict__ slots, const uint32_t* _
         s_head[16 + i] = (uint8_t)((uint32_t)g.w >> (24 - 8 * i));
         s_head[20 + i] = (uint8_t)((uint32_t)g.h >> (24 - 8 * i));
       }
-      s_head[24] = 8; s_head[25] = 2; s_head[26] = 0; s_head[27] = 0; s_head[28] = 0;
+      s_head[24] = 8; s_head[25] = g.bpp == 4 ? 6 : 2; s_head[26] = 0; s_head[27] = 0; s_head[28] = 0;
       uint32_t r = 0xFFFFFFFFu;
       for (int i = 12; i < 29; ++i) r = dd_crc_byte(r, s_head[i]);
       r ^= 0xFFFFFFFFu;
@@ -657,24 +659,26 @@ void dd_png_assemble_kernel(const uint8_t* __restrict__ slots, const uint32_t* _
 
 }  // namespace
 
-extern "C" int64_t dd_png_workspace_bytes(int32_t m, int32_t h, int32_t w) {
-  if (m <= 0 || m > 65535 || h <= 0 || w <= 0) return -1;
+extern "C" int64_t dd_png_workspace_bytes_c(int32_t m, int32_t h, int32_t w, int32_t channels) {
+  if (m <= 0 || m > 65535 || h <= 0 || w <= 0 || (channels != 3 && channels != 4)) return -1;
   Geom g;
   Layout l;
-  if (!geometry(m, h, w, &g, &l)) return -1;
+  if (!geometry(m, h, w, channels, &g, &l)) return -1;
   return l.total;
 }
 
-extern "C" int dd_png_encode_u8(const uint8_t* frames, int32_t m, int32_t h, int32_t w, void* workspace,
-                                int64_t workspace_bytes, uint8_t* out, int64_t capacity, int32_t* lengths,
-                                dd_stream_t stream) {
+extern "C" int64_t dd_png_workspace_bytes(int32_t m, int32_t h, int32_t w) { return dd_png_workspace_bytes_c(m, h, w, 3); }
+
+extern "C" int dd_png_encode_u8c(const uint8_t* frames, int32_t m, int32_t h, int32_t w, int32_t channels, void* workspace,
+                                 int64_t workspace_bytes, uint8_t* out, int64_t capacity, int32_t* lengths,
+                                 dd_stream_t stream) {
   if (!frames || !workspace || !out || !lengths) return DD_ERR_BAD_ARG;
-  if (m <= 0 || h <= 0 || w <= 0) return DD_ERR_BAD_ARG;
+  if (m <= 0 || h <= 0 || w <= 0 || (channels != 3 && channels != 4)) return DD_ERR_BAD_ARG;
   if (capacity < kFileFixed) return DD_ERR_BAD_ARG;
   if (!dd_aligned16(workspace) || (reinterpret_cast<uintptr_t>(lengths) & 3u)) return DD_ERR_BAD_ARG;
   Geom g;
   Layout l;
-  if (!geometry(m, h, w, &g, &l) || m > 65535) return DD_ERR_UNSUPPORTED;
+  if (!geometry(m, h, w, channels, &g, &l) || m > 65535) return DD_ERR_UNSUPPORTED;
   if (workspace_bytes < l.total) return DD_ERR_BAD_ARG;
   uint8_t* ws = reinterpret_cast<uint8_t*>(workspace);
   uint8_t* filt = ws + l.filt;
@@ -690,4 +694,10 @@ extern "C" int dd_png_encode_u8(const uint8_t* frames, int32_t m, int32_t h, int
   hipLaunchKernelGGL(dd_png_assemble_kernel, dim3((unsigned)g.nchunk + 1, (unsigned)m), dim3(kThreads), 0, s, slots, info, off,
                      frame, out, capacity, lengths, g);
   return dd_check_launch();
+}
+
+extern "C" int dd_png_encode_u8(const uint8_t* frames, int32_t m, int32_t h, int32_t w, void* workspace,
+                                int64_t workspace_bytes, uint8_t* out, int64_t capacity, int32_t* lengths,
+                                dd_stream_t stream) {
+  return dd_png_encode_u8c(frames, m, h, w, 3, workspace, workspace_bytes, out, capacity, lengths, stream);
 }

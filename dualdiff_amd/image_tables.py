@@ -218,7 +218,8 @@ def png_unit_lut():
     return torch.arange(256).float().div(255).contiguous()
 
 
-def png_capacity(h, w):
-    """The longest file of an (h, w) frame: every chunk stored.  No content makes a file longer."""
-    n = int(h) * (1 + 3 * int(w))
+def png_capacity(h, w, channels=3):
+    """The longest file of an (h, w) frame of 3 (RGB) or 4 (RGBA) channels: every chunk stored.  No content makes a file
+    longer."""
+    n = int(h) * (1 + int(channels) * int(w))
     return PNG_FILE_FIXED + PNG_CHUNK_FIXED * (-(-n // PNG_CHUNK)) + n

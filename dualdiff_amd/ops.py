@@ -535,38 +535,52 @@ def png_encode_u8(frames, out=None, capacity=None):
     length above the capacity is the file's true length and the row then holds its first `capacity` bytes.  Nothing is read
     back and no table comes from the host.  The scratch buffer is ops.workspace's: call once, on the capture stream or
     under the same workspace_owner, before capturing the launches in a graph."""
-    what = "png_encode_u8"
-    if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
-        raise ValueError("%s takes an (m, H, W, 3) frame batch, got %s" % (what, tuple(frames.shape)))
+    return _png_encode("png_encode_u8", (3,), frames, out, capacity)
+
+
+def png_encode_u8c(frames, out=None, capacity=None):
+    """png_encode_u8 for uint8 frames of 3 or 4 channels, (m, H, W, 3) or (m, H, W, 4) (dd_png_encode_u8c): the same format
+    with colour type 6 and four bytes per pixel in the filters for RGBA; capacity defaults to
+    image_tables.png_capacity(H, W, channels).  RGB frames give png_encode_u8's bytes."""
+    return _png_encode("png_encode_u8c", (3, 4), frames, out, capacity)
+
+
+def _png_encode(what, channels, frames, out, capacity):
+    """The two wrappers above: `channels` is what the last dimension may be.  png_encode_u8 stays on the entry points it
+    has always used, png_encode_u8c goes through the ones that take the channel count."""
+    if frames.dim() != 4 or frames.shape[3] not in channels or frames.numel() == 0:
+        raise ValueError("%s takes an (m, H, W, %s) frame batch, got %s" % (what, " or ".join(map(str, channels)), tuple(frames.shape)))
     if frames.dtype != torch.uint8:
         raise ValueError("%s takes uint8 frames, got %s" % (what, frames.dtype))
     if not frames.is_contiguous():
         raise ValueError("%s takes a contiguous NHWC tensor" % what)
-    m, h, w = frames.shape[0], frames.shape[1], frames.shape[2]
+    m, h, w, ch = frames.shape
     if out is not None:
         if out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != m or not out.is_contiguous():
             raise ValueError("%s: out must be a contiguous uint8 (%d, capacity) tensor" % (what, m))
         if capacity is not None and int(capacity) != out.shape[1]:
             raise ValueError("%s: capacity %r does not match out %s" % (what, capacity, tuple(out.shape)))
         capacity = out.shape[1]
-    capacity = png_capacity(h, w) if capacity is None else int(capacity)
+    capacity = png_capacity(h, w, ch) if capacity is None else int(capacity)
     if capacity < PNG_FILE_FIXED:
         raise ValueError("%s: capacity must be at least the fixed parts of a file (%d bytes), got %d"
                          % (what, PNG_FILE_FIXED, capacity))
     _need_gpu(frames, out)
     lib = _native.load()
-    need = lib.dd_png_workspace_bytes(m, h, w)
+    generic = channels != (3,)
+    need = lib.dd_png_workspace_bytes_c(m, h, w, ch) if generic else lib.dd_png_workspace_bytes(m, h, w)
     if need < 0:
         raise _native.Unsupported("dualdiff_amd.%s: %d frames of %d x %d are more than one call takes" % (what, m, h, w))
     if out is None:
         out = torch.empty((m, capacity), dtype=torch.uint8, device=frames.device)
     lengths = torch.empty((m,), dtype=torch.int32, device=frames.device)
     ws = workspace(need, frames.device, kind="png")
-    _timer.launch(what, lib.dd_png_encode_u8, _ptr(frames), m, h, w, _ptr(ws), ws.numel() * 4, _ptr(out), capacity,
-                  _ptr(lengths), _stream(),
+    head = (_ptr(frames), m, h, w) + ((ch,) if generic else ())
+    _timer.launch(what, lib.dd_png_encode_u8c if generic else lib.dd_png_encode_u8, *head, _ptr(ws), ws.numel() * 4,
+                  _ptr(out), capacity, _ptr(lengths), _stream(),
                   # frames read twice by the filter, the filtered bytes written once and read once; the chunks' deflate
                   # forms are as long as the content makes them and are not booked
-                  book=lambda: ("dd_png_encode", 0.0, float(2 * frames.numel() + 2 * m * h * (1 + 3 * w))))
+                  book=lambda: ("dd_png_encode", 0.0, float(2 * frames.numel() + 2 * m * h * (1 + ch * w))))
     return out, lengths
 
 
@@ -787,6 +801,102 @@ def box_views(corners, labels, offsets, transforms, views, cap, points_mode="all
                   *(_ptr(t) for t in out), _stream(),
                   book=lambda: ("dd_box_views_kernel", 0.0,
                                 float((1 if fm == 0 else views) * total * 96 + out[0].numel() * 4 + out[1].numel() * 9)))
+    return out
+
+
+BOX_EDGES_MAX = 1024                             # include/dualdiff_hip.h: DD_BOX_EDGES_MAX, the boxes of one scene
+BOX_FLAGS = ((1, "a label outside [-n_classes, n_classes): that box is not drawn"),
+             (2, "a projected coordinate beyond +-2^29, saturated there"),
+             (4, "a view drew more boxes than cap, or a scene holds more than %d" % BOX_EDGES_MAX))
+
+
+def box_edges(corners, labels, offsets, transforms, cap, n_classes):
+    """Every scene's box corners -> per (scene, view) the integer end points of the boxes drawn in that view, in draw
+    order, in one launch (include/dualdiff_hip.h: dd_box_edges; runner/box_visualizer.py:89-114).  corners (total, 8, 3)
+    fp32 (the re-centred ones), labels (total,) int64, offsets (scenes + 1,) int32, transforms (scenes, views, 4, 4) fp32
+    — contiguous device tensors.  cap: slots per (scene, view), at most BOX_EDGES_MAX.
+    -> (pts (scenes, views, cap, 8, 2) int32, cls (scenes, views, cap) int32, counts (scenes, views) int32, flags (1,)
+    int32: an OR of BOX_FLAGS' bits).  Nothing is read back."""
+    what = "box_edges"
+    if corners.dim() != 3 or tuple(corners.shape[1:]) != (8, 3) or corners.dtype != torch.float32:
+        raise ValueError("%s takes fp32 corners (total, 8, 3), got %s %s" % (what, corners.dtype, tuple(corners.shape)))
+    total = corners.shape[0]
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (total,):
+        raise ValueError("%s takes int64 labels (%d,), got %s %s" % (what, total, labels.dtype, tuple(labels.shape)))
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.shape[0] < 2:
+        raise ValueError("%s takes int32 offsets (scenes + 1,), got %s %s" % (what, offsets.dtype, tuple(offsets.shape)))
+    scenes = offsets.shape[0] - 1
+    if transforms.dtype != torch.float32 or transforms.dim() != 4 or transforms.shape[1] == 0 \
+            or (transforms.shape[0],) + tuple(transforms.shape[2:]) != (scenes, 4, 4):
+        raise ValueError("%s takes fp32 transforms (%d, views, 4, 4), got %s %s"
+                         % (what, scenes, transforms.dtype, tuple(transforms.shape)))
+    views, cap, n_classes = transforms.shape[1], int(cap), int(n_classes)
+    if cap <= 0 or n_classes <= 0:
+        raise ValueError("%s: cap and n_classes must be positive, got %d and %d" % (what, cap, n_classes))
+    if cap > BOX_EDGES_MAX:
+        raise _native.Unsupported("dualdiff_amd.%s: a scene holds at most %d boxes, got cap = %d" % (what, BOX_EDGES_MAX, cap))
+    ins = (corners, labels, offsets, transforms)
+    if any(not t.is_contiguous() for t in ins):
+        raise ValueError("%s takes contiguous tensors" % what)
+    _need_gpu(*ins)
+    dev = corners.device
+    pts = torch.empty((scenes, views, cap, 8, 2), dtype=torch.int32, device=dev)
+    cls = torch.empty((scenes, views, cap), dtype=torch.int32, device=dev)
+    counts = torch.empty((scenes, views), dtype=torch.int32, device=dev)
+    flags = torch.empty((1,), dtype=torch.int32, device=dev)
+    lib = _native.load()
+    _timer.launch(what, lib.dd_box_edges, _ptr(corners), _ptr(labels), _ptr(offsets), _ptr(transforms), total, scenes,
+                  views, cap, n_classes, _ptr(pts), _ptr(cls), _ptr(counts), _ptr(flags), _stream(),
+                  book=lambda: ("dd_box_edges_kernel", 0.0, float(2 * views * total * 104 + pts.numel() * 4 + cls.numel() * 4)))
+    return pts, cls, counts, flags
+
+
+def box_draw_u8(frames, pts, cls, counts, palette, transparent=False, size=None):
+    """The boxes of box_edges drawn over uint8 frames, or alone on a transparent canvas, in one launch (include/
+    dualdiff_hip.h: dd_box_draw_u8): every box's 12 edges as PIL's thin line, the last box of a row on top.  frames (m,
+    H, W, 3) uint8, m = scenes * views, or None with transparent=True and size=(H, W); pts (m, cap, 8, 2) int32 (or
+    (scenes, views, cap, 8, 2)), cls (m, cap) int32, counts (m,) int32; palette (n, 3) uint8: RGB per class — contiguous
+    device tensors.  -> (m, H, W, 3) uint8, a new tensor (the frames are not written), or (m, H, W, 4) RGBA with
+    transparent=True: A = 255 where a line of a colour other than black lies."""
+    what = "box_draw_u8"
+    if pts.dtype != torch.int32 or pts.dim() not in (4, 5) or tuple(pts.shape[-2:]) != (8, 2) or pts.numel() == 0:
+        raise ValueError("%s takes int32 pts (m, cap, 8, 2), got %s %s" % (what, pts.dtype, tuple(pts.shape)))
+    cap = pts.shape[-3]
+    m = pts.numel() // (cap * 16)
+    if cls.dtype != torch.int32 or cls.numel() != m * cap or counts.dtype != torch.int32 or counts.numel() != m:
+        raise ValueError("%s takes int32 cls (%d, %d) and counts (%d,), got %s %s and %s %s"
+                         % (what, m, cap, m, cls.dtype, tuple(cls.shape), counts.dtype, tuple(counts.shape)))
+    if palette.dtype != torch.uint8 or palette.dim() != 2 or palette.shape[1] != 3 or palette.shape[0] == 0:
+        raise ValueError("%s takes a uint8 palette (n, 3), got %s %s" % (what, palette.dtype, tuple(palette.shape)))
+    transparent = bool(transparent)
+    if frames is None:
+        if not transparent:
+            raise ValueError("%s: frames may be None with transparent=True only" % what)
+        try:
+            h, w = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError("%s: without frames pass size=(H, W), got %r" % (what, size))
+        if h <= 0 or w <= 0:
+            raise ValueError("%s: size must be positive, got %r" % (what, size))
+    else:
+        if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0 or frames.dtype != torch.uint8:
+            raise ValueError("%s takes uint8 frames (m, H, W, 3), got %s %s" % (what, frames.dtype, tuple(frames.shape)))
+        if frames.shape[0] != m:
+            raise ValueError("%s: %d frames for %d rows of boxes" % (what, frames.shape[0], m))
+        h, w = frames.shape[1], frames.shape[2]
+        if size is not None and tuple(int(v) for v in size) != (h, w):
+            raise ValueError("%s: size %r does not match the frames' %d x %d" % (what, size, h, w))
+    ins = (frames, pts, cls, counts, palette)
+    if any(t is not None and not t.is_contiguous() for t in ins):
+        raise ValueError("%s takes contiguous tensors" % what)
+    _need_gpu(*ins)
+    if h >= 1 << 15 or w >= 1 << 15 or m > 65535:
+        raise _native.Unsupported("dualdiff_amd.%s: %d frames of %d x %d are more than one call takes" % (what, m, h, w))
+    out = torch.empty((m, h, w, 4 if transparent else 3), dtype=torch.uint8, device=pts.device)
+    lib = _native.load()
+    _timer.launch(what, lib.dd_box_draw_u8, _ptr(None if transparent else frames), _ptr(pts), _ptr(cls), _ptr(counts),
+                  _ptr(palette), _ptr(out), m, cap, h, w, palette.shape[0], 1 if transparent else 0, _stream(),
+                  book=lambda: ("dd_box_draw_kernel", 0.0, float(out.numel() + (0 if transparent else out.numel()))))
     return out
 
 

@@ -1,10 +1,13 @@
-"""The pipeline's modules are imported by their dotted paths; `MapRender` (map_output.py) is also a name of the package,
-resolved on first use so that importing one module does not import the others."""
+"""The pipeline's modules are imported by their dotted paths; `MapRender` (map_output.py) and `BoxOverlay`
+(box_output.py) are also names of the package, resolved on first use so that importing one module does not import the
+others."""
+
+_LAZY = {"MapRender": "map_output", "BoxOverlay": "box_output"}
 
 
 def __getattr__(name):
-    if name in ("MapRender", "map_output"):
+    if name in _LAZY or name in _LAZY.values():
         import importlib
-        mod = importlib.import_module(".map_output", __name__)
-        return mod if name == "map_output" else mod.MapRender
+        mod = importlib.import_module("." + _LAZY.get(name, name), __name__)
+        return mod if name in _LAZY.values() else getattr(mod, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -203,6 +203,29 @@ def encode_png(u8, **options):
     return [files[i * per:(i + 1) * per] for i in range(u8.shape[0])]
 
 
+@torch.no_grad()
+def encode_png_rgba(u8):
+    """encode_png for RGBA frames, (b, n, H, W, 4) or (m, H, W, 4) uint8 — the transparent box overlays of
+    pipeline/box_output.py: colour type 6, otherwise the same format (`ops.png_encode_u8c`).  The files open as mode
+    "RGBA" and decode to exactly the frames."""
+    if u8.dtype != torch.uint8 or u8.dim() not in (4, 5) or u8.shape[-1] != 4 or u8.numel() == 0:
+        raise ValueError("encode_png_rgba takes uint8 frames (b, n, H, W, 4) or (m, H, W, 4), got %s %s" % (tuple(u8.shape), u8.dtype))
+    frames = (u8.flatten(0, 1) if u8.dim() == 5 else u8).contiguous()
+    buf, lengths = O.png_encode_u8c(frames)
+    n = lengths.cpu().tolist()
+    raw = buf[:, :max(n)].cpu().numpy()
+    files = [raw[i, :k].tobytes() for i, k in enumerate(n)]
+    if u8.dim() == 4:
+        return files
+    per = u8.shape[1]
+    return [files[i * per:(i + 1) * per] for i in range(u8.shape[0])]
+
+
+def save_png_rgba(u8, paths):
+    """encode_png_rgba, each file written to its path, as save_png does."""
+    return _save(encode_png_rgba(u8), u8, paths, "save_png_rgba")
+
+
 def save_png(u8, paths, **options):
     """encode_png, each file written to its path: `paths` nested as the frames are ((b, n) names, or m names).  Missing
     directories are created.  Returns the files' sizes, nested the same way."""
@@ -211,14 +234,15 @@ def save_png(u8, paths, **options):
 
 def concat_views(u8, oneline=False):
     """The reference's `concat_6_views` (runner/img_utils.py:5-40) for equal-sized views, on the tensor's device: frames
-    (b, 6, H, W, 3) -> (b, 2 H, 3 W, 3), views 0-2 over views 3-5; oneline=True: (b, n, H, W, 3), n >= 2 -> (b, H, n W, 3)."""
-    if u8.dim() != 5 or u8.shape[-1] != 3:
-        raise ValueError("concat_views takes frames (b, n, H, W, 3), got %s" % (tuple(u8.shape),))
-    b, n, h, w, _ = u8.shape
+    (b, 6, H, W, 3) -> (b, 2 H, 3 W, 3), views 0-2 over views 3-5; oneline=True: (b, n, H, W, 3), n >= 2 -> (b, H, n W, 3).
+    A last dimension of 4 (the RGBA box overlays) is kept."""
+    if u8.dim() != 5 or u8.shape[-1] not in (3, 4):
+        raise ValueError("concat_views takes frames (b, n, H, W, 3) or (b, n, H, W, 4), got %s" % (tuple(u8.shape),))
+    b, n, h, w, c = u8.shape
     if oneline:
         if n < 2:
             raise ValueError("concat_views(oneline=True) takes at least 2 views, got %d" % n)
-        return u8.permute(0, 2, 1, 3, 4).reshape(b, h, n * w, 3)
+        return u8.permute(0, 2, 1, 3, 4).reshape(b, h, n * w, c)
     if n != 6:
         raise ValueError("concat_views takes 6 views for the 2 x 3 grid, got %d (oneline=True takes any n >= 2)" % n)
-    return u8.reshape(b, 2, 3, h, w, 3).permute(0, 1, 3, 2, 4, 5).reshape(b, 2 * h, 3 * w, 3)
+    return u8.reshape(b, 2, 3, h, w, c).permute(0, 1, 3, 2, 4, 5).reshape(b, 2 * h, 3 * w, c)

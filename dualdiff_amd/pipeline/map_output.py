@@ -24,8 +24,8 @@ pipeline/image_output.py take a batch of those.
 
 A quirk that is kept: `argmax` is 0 where no dynamic layer is set, so with dynamic layers present the first object class
 is in the legend of every map that has a pixel free of objects (:127-128).  Only square maps are accepted: a non-square
-picture goes through PIL's affine `rotate`, which is not built.  The box overlays (`show_box_on_views`) stay with the
-caller.
+picture goes through PIL's affine `rotate`, which is not built.  The box overlays (`show_box_on_views`) are
+pipeline/box_output.py.
 """
 import numpy as np
 import torch

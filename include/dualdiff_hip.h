@@ -592,6 +592,13 @@ int dd_jpeg_encode_u8(const uint8_t* frames, int32_t m, int32_t h, int32_t w, co
 int64_t dd_png_workspace_bytes(int32_t m, int32_t h, int32_t w);
 int dd_png_encode_u8(const uint8_t* frames, int32_t m, int32_t h, int32_t w, void* workspace, int64_t workspace_bytes,
                      uint8_t* out, int64_t capacity, int32_t* lengths, dd_stream_t stream);
+/* The same for frames of `channels` bytes per pixel, uint8 [m][h][w][channels]: 3 is dd_png_encode_u8 (the same bytes), 4
+ * is RGBA — colour type 6, the filters' left neighbour four bytes back, n = h * (1 + 4 * w) in the bound above.  The
+ * RGBA box overlays (dd_box_draw_u8, transparent = 1) are saved through it.  Any other `channels`: DD_ERR_BAD_ARG (-1 from
+ * dd_png_workspace_bytes_c); everything else as above. */
+int64_t dd_png_workspace_bytes_c(int32_t m, int32_t h, int32_t w, int32_t channels);
+int dd_png_encode_u8c(const uint8_t* frames, int32_t m, int32_t h, int32_t w, int32_t channels, void* workspace,
+                      int64_t workspace_bytes, uint8_t* out, int64_t capacity, int32_t* lengths, dd_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * JPEG input (csrc/jpeg_decode.hip, csrc/jpeg_decode_core.h): the entropy-coded segments of m baseline .jpg files of one
@@ -741,6 +748,65 @@ int dd_map_render_u8(const uint8_t* maps, const float* stab, const float* dtab, 
                      int32_t c, int32_t s, int32_t ns, int32_t nd, dd_stream_t stream);
 int dd_map_compose_u8(const uint8_t* src, const int32_t* index, const uint8_t* legend, uint8_t* out, int32_t m, int32_t g,
                       int32_t t, int32_t lh, int32_t lw, int32_t side, dd_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
+ * Box output (csrc/box_overlay.hip, csrc/box_overlay_core.h): the 3D-box overlays of the reference's demo path
+ * (misc/test_utils.py:48-65 draw_box_on_imgs -> runner/box_visualizer.py:89-114 show_box_on_views; tools/test.py:86-97
+ * saves them as `{n}_ori_box.png` / `{n}_gen{t}_box.png`).  The geometry is the reference's.  The line is PIL's thin line
+ * (`ImageDraw.line(..., width=1)`), not the anti-aliased `cv2.line(..., LINE_AA)` the reference draws through mmdet3d: the
+ * pictures differ from the reference's in the anti-aliasing fringe of the 1-pixel lines, and only there.
+ *
+ * dd_box_edges: one launch, no host synchronisation.  Inputs as dd_box_views takes them (device):
+ *   corners    [total][8][3] fp32: the boxes re-centred to (0.5, 0.5, 0.5) (runner/box_visualizer.py:94);
+ *   labels     [total] int64;  offsets [scenes + 1] int32 (clamped as dd_box_views clamps them);
+ *   transforms [scenes][views][4][4] fp32, row-major: img_aug_matrix @ lidar2image (:102-104).
+ *  G1 (x, y, z) = rows 0..2 of the matrix (promoted to double) * (corner promoted to double, 1.0), summed as dd_box_views
+ *     sums (fused multiply-adds from the translation column on): a quantity within rounding of a threshold or of an
+ *     integer may come out differently under another summation order.
+ *  G2 a box is drawn in a view iff all 8 of its z are > 0 and its label lies in [-n_classes, n_classes).
+ *  G3 draw order: descending least z of the box (farthest first), ties to the lower index.
+ *  G4 zc = clip(z, 1e-5, 1e5), u = x / zc, v = y / zc (IEEE double); the integer point is u, v truncated toward zero;
+ *     a value beyond +-2^29 is stored as +-2^29 (a NaN as -2^29) and sets DD_BOX_FLAG_SATURATED.
+ *  G6 the class is the label, a negative one + n_classes (Python's indexing).
+ * Out, for every (scene, view), rows of `cap` slots in draw order:
+ *   pts    [scenes][views][cap][8][2] int32, 16-byte aligned: (x, y) of corner 0..7; slots past the count are zero;
+ *   cls    [scenes][views][cap] int32: the class in [0, n_classes); zero past the count;
+ *   counts [scenes][views] int32: the number of boxes drawn, also when it exceeds cap — then the nearest `cap` are in the
+ *          row (the last `cap` of the draw order) and DD_BOX_FLAG_CAP is set;
+ *   flags  [1] int32: whatever it held before, an OR of DD_BOX_FLAG_* over the launch (cleared on the stream, then at
+ *          most one vector atomic OR per wave).  DD_BOX_FLAG_SATURATED is set for boxes that are in a row only.
+ * A scene holds at most DD_BOX_EDGES_MAX boxes: of a longer one the first DD_BOX_EDGES_MAX are read and DD_BOX_FLAG_CAP
+ * is set.  DD_ERR_BAD_ARG, before any runtime call: a NULL pointer (corners / labels may be NULL when total == 0),
+ * total < 0, non-positive scenes / views / cap / n_classes, a pointer that is not aligned to its element (pts: 16
+ * bytes).  cap > DD_BOX_EDGES_MAX or scenes * views >= 2^31: DD_ERR_UNSUPPORTED.
+ *
+ * dd_box_draw_u8: one launch, no host synchronisation, deterministic (no atomics).
+ *   frames  uint8 [m][h][w][3] (device), m = scenes * views; NULL is allowed with transparent = 1 (not read then);
+ *   pts, cls, counts: as dd_box_edges writes them (a count is clamped to [0, cap], a point to +-2^29, a class to
+ *           [0, n_palette));  palette uint8 [n_palette][3] (device): RGB per class;
+ *   out     uint8 [m][h][w][3], or [m][h][w][4] with transparent = 1 (then 4-byte aligned).
+ *  G5 a box is its 12 edges (0,1) (0,3) (0,4) (1,2) (1,5) (3,2) (3,7) (4,5) (4,7) (2,6) (5,6) (6,7), each PIL's thin
+ *     line FROM its first corner TO its second (the line is not symmetric in its end points): with dx = |x1 - x0|,
+ *     dy = |y1 - y0|, xs, ys = +-1 (+1 when the end is >= the start) and i = 0 .. max(dx, dy), the pixels
+ *     (x0 + xs i, y0 + ys floor((2 dy i + dx) / (2 dx))) for dx >= dy (dx == 0: the one pixel (x0, y0)), else
+ *     (x0 + xs floor((2 dx i + dy) / (2 dy)), y0 + ys i).  Nothing is clipped: a pixel asks every line whether it is on it.
+ *  G7 a pixel has the colour of the last box in slot order with an edge that covers it; lines are opaque.
+ *  G8 transparent = 0: every other pixel is the frame's.  transparent = 1: the boxes on black, A = 255 where any of
+ *     R, G, B is > 0, else 0 (misc/test_utils.py:49-64).
+ * DD_ERR_BAD_ARG, before any runtime call: a NULL pts / cls / counts / palette / out, NULL frames with transparent = 0,
+ * transparent not 0 / 1, non-positive m / cap / h / w / n_palette, a misaligned pts (16), cls, counts (4) or RGBA out
+ * (4).  h or w >= 2^15, m > 65535 or m * cap >= 2^40: DD_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------- */
+#define DD_BOX_EDGES_MAX 1024
+#define DD_BOX_FLAG_LABEL 1      /* a label outside [-n_classes, n_classes): that box is not drawn */
+#define DD_BOX_FLAG_SATURATED 2  /* a coordinate beyond +-2^29 */
+#define DD_BOX_FLAG_CAP 4        /* a view drew more than cap boxes, or a scene held more than DD_BOX_EDGES_MAX */
+int dd_box_edges(const float* corners, const int64_t* labels, const int32_t* offsets, const float* transforms,
+                 int32_t total, int32_t scenes, int32_t views, int32_t cap, int32_t n_classes, int32_t* pts, int32_t* cls,
+                 int32_t* counts, int32_t* flags, dd_stream_t stream);
+int dd_box_draw_u8(const uint8_t* frames, const int32_t* pts, const int32_t* cls, const int32_t* counts,
+                   const uint8_t* palette, uint8_t* out, int32_t m, int32_t cap, int32_t h, int32_t w, int32_t n_palette,
+                   int32_t transparent, dd_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * CLIP text encoder (csrc/clip.hip): the SD-v1.5 `text_encoder` (transformers.CLIPTextModel) that the reference calls at
