@@ -177,6 +177,9 @@ SIGNATURES = {
                                    c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "dd_png_condition": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                    c_int32, c_int32, c_void_p]),
+    "dd_png_condition_resize": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                          c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                          c_int32, c_void_p]),
     "dd_map_render_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                    c_int32, c_void_p]),
     "dd_map_compose_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,

@@ -24,6 +24,9 @@
 // same tables in LDS, the same values, so control flow never diverges.  Lane 0 reads a block's header and builds its tables;
 // literals go to the window by lane 0, a match is copied by all lanes at once (byte i of it is window[pos - dist + i % dist],
 // all of which stand before the match), and the window goes to global memory 4 KiB at a time.
+//
+// The condition is one launch on top: dd_png_condition_kernel (stack and per-view crop), or, for image_size [192, 384],
+// dd_png_condition_resize_kernel (crop_drivewm: per view a zero row on top, a bilinear resize, a crop).
 #include "dd_common.h"
 #include "png_decode_core.h"
 
@@ -409,6 +412,97 @@ void dd_png_condition_kernel(const uint8_t* __restrict__ frames, float* __restri
   }
 }
 
+// crop_drivewm's pad, resize and crop (dataset/utils.py:355-358, 374-388) per view: what the kernel below is told
+struct Resize {
+  int h, w, pw;                                // the frames; pw = w / views
+  int pad;                                     // zero rows above every view
+  int top, left, oh, ow;                       // the crop of the resized view
+  int row;                                     // views * ow: one row of the output
+};
+
+// One output element: the bilinear sample of the padded view at resized row top + oy, column left + ox % ow.  The taps and
+// weights of both axes come from the host's float32 tables; the combination is spelled out operation by operation — the
+// horizontal pair of each row first, products rounded on their own, the sums fused — so that the compiler's contraction has
+// nothing to decide.  A tap is clamped to the padded view whatever the tables hold.
+__device__ __forceinline__ float dd_pngc_sample(const uint8_t* __restrict__ frames, const float* __restrict__ lut,
+                                                const int32_t* __restrict__ ridx, const float* __restrict__ rlam,
+                                                const int32_t* __restrict__ cidx, const float* __restrict__ clam,
+                                                const Resize& g, int64_t b, int c, int oy, int ox) {
+  const int v = ox / g.ow, x = g.left + ox - v * g.ow, y = g.top + oy;
+  const int y0 = min(max(ridx[2 * y], 0), g.h + g.pad - 1), y1 = min(max(ridx[2 * y + 1], 0), g.h + g.pad - 1);
+  const int x0 = min(max(cidx[2 * x], 0), g.pw - 1), x1 = min(max(cidx[2 * x + 1], 0), g.pw - 1);
+  const float a0 = rlam[2 * y], a1 = rlam[2 * y + 1], b0 = clam[2 * x], b1 = clam[2 * x + 1];
+  const uint8_t* view = frames + (b * g.h * g.w + (int64_t)v * g.pw) * 3 + c;
+  float A = 0.0f, B = 0.0f, C = 0.0f, D = 0.0f;              // a padded row is 0.0f
+  if (y0 >= g.pad) {
+    const uint8_t* r = view + (int64_t)(y0 - g.pad) * g.w * 3;
+    A = lut[r[x0 * 3]];
+    B = lut[r[x1 * 3]];
+  }
+  if (y1 >= g.pad) {
+    const uint8_t* r = view + (int64_t)(y1 - g.pad) * g.w * 3;
+    C = lut[r[x0 * 3]];
+    D = lut[r[x1 * 3]];
+  }
+  const float t = __fmaf_rn(b0, A, __fmul_rn(b1, B));
+  const float u = __fmaf_rn(b0, C, __fmul_rn(b1, D));
+  return __fmaf_rn(a0, t, __fmul_rn(a1, u));
+}
+
+// element i of the output [b][3][oh][row] -> its sample, plane, row and column
+template <typename T>
+__device__ __forceinline__ void dd_pngc_place(T i, const Resize& g, int* ox, int* oy, int* c, int64_t* b) {
+  *ox = (int)(i % (T)g.row);
+  T r = i / (T)g.row;
+  *oy = (int)(r % (T)g.oh);
+  r /= (T)g.oh;
+  *c = (int)(r % 3);
+  *b = (int64_t)(r / 3);
+}
+
+// One thread per four consecutive floats of the output taken as one flat array, so that every store but the last is a
+// full 16-byte store whatever views * ow is (a run may cross from one output row into the next); the last run of a total
+// that is no multiple of four is stored float by float.
+__global__ __launch_bounds__(kThreads)
+void dd_png_condition_resize_kernel(const uint8_t* __restrict__ frames, float* __restrict__ out, const float* __restrict__ lut,
+                                    const int32_t* __restrict__ ridx, const float* __restrict__ rlam,
+                                    const int32_t* __restrict__ cidx, const float* __restrict__ clam, int64_t total,
+                                    Resize g) {
+  const int64_t runs = (total + 3) / 4;
+  for (int64_t run = (int64_t)blockIdx.x * kThreads + threadIdx.x; run < runs; run += (int64_t)gridDim.x * kThreads) {
+    const int64_t i = run * 4;
+    int ox, oy, c;
+    int64_t b;
+    if (total <= 0x7fffffff) dd_pngc_place<uint32_t>((uint32_t)i, g, &ox, &oy, &c, &b);      // uniform: 32-bit divisions
+    else dd_pngc_place<int64_t>(i, g, &ox, &oy, &c, &b);
+    const int n = (int)min((int64_t)4, total - i);
+    float val[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k < n) {
+        val[k] = dd_pngc_sample(frames, lut, ridx, rlam, cidx, clam, g, b, c, oy, ox);
+        if (++ox == g.row) {                                 // on to the next row, plane, sample
+          ox = 0;
+          if (++oy == g.oh) {
+            oy = 0;
+            if (++c == 3) {
+              c = 0;
+              ++b;
+            }
+          }
+        }
+      }
+    }
+    if (n == 4) {
+      *reinterpret_cast<float4*>(out + i) = make_float4(val[0], val[1], val[2], val[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        if (k < n) out[i + k] = val[k];
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int64_t dd_png_decode_workspace_bytes(int32_t m, int32_t h, int32_t w) {
@@ -468,5 +562,31 @@ extern "C" int dd_png_condition(const uint8_t* frames, float* out, const float* 
   hipLaunchKernelGGL(dd_png_condition_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(kThreads), 0,
                      dd_stream(stream), frames, out, lut, total, (int)h, (int)w, (int)views, (int)top, (int)left, (int)oh,
                      (int)ow);
+  return dd_check_launch();
+}
+
+extern "C" int dd_png_condition_resize(const uint8_t* frames, float* out, const float* lut, const int32_t* row_taps,
+                                       const float* row_weights, const int32_t* col_taps, const float* col_weights,
+                                       int32_t b, int32_t h, int32_t w, int32_t views, int32_t pad_top, int32_t rh,
+                                       int32_t rw, int32_t top, int32_t left, int32_t oh, int32_t ow, dd_stream_t stream) {
+  if (!frames || !out || !lut || !row_taps || !row_weights || !col_taps || !col_weights) return DD_ERR_BAD_ARG;
+  if (b <= 0 || h <= 0 || w <= 0 || views <= 0 || rh <= 0 || rw <= 0 || oh <= 0 || ow <= 0) return DD_ERR_BAD_ARG;
+  if (pad_top < 0 || top < 0 || left < 0) return DD_ERR_BAD_ARG;
+  if (w % views != 0 || (int64_t)top + oh > rh || (int64_t)left + ow > rw) return DD_ERR_BAD_ARG;
+  if (!dd_aligned16(out) || reinterpret_cast<uintptr_t>(lut) & 3u || reinterpret_cast<uintptr_t>(row_taps) & 3u ||
+      reinterpret_cast<uintptr_t>(row_weights) & 3u || reinterpret_cast<uintptr_t>(col_taps) & 3u ||
+      reinterpret_cast<uintptr_t>(col_weights) & 3u)
+    return DD_ERR_BAD_ARG;
+  // 32-bit positions inside a frame and inside an output row; 64-bit ones across the batch
+  if ((int64_t)h + pad_top > 0x7fffffff || (int64_t)h * w * 3 > 0x7fffffff || (int64_t)views * ow > 0x7fffffff)
+    return DD_ERR_UNSUPPORTED;
+  if ((int64_t)b * h * w * 3 > ((int64_t)1 << 40) || (int64_t)b * 3 * oh * views * ow > ((int64_t)1 << 40))
+    return DD_ERR_UNSUPPORTED;
+  const int64_t total = (int64_t)b * 3 * oh * views * ow;
+  const int64_t blocks = ((total + 3) / 4 + kThreads - 1) / kThreads;
+  const Resize g = {(int)h, (int)w, (int)(w / views), (int)pad_top, (int)top, (int)left, (int)oh, (int)ow, (int)(views * ow)};
+  dd_clear_error();
+  hipLaunchKernelGGL(dd_png_condition_resize_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(kThreads), 0,
+                     dd_stream(stream), frames, out, lut, row_taps, row_weights, col_taps, col_weights, total, g);
   return dd_check_launch();
 }

@@ -1,7 +1,7 @@
 """Host-side builders of the constants the image and JPEG kernels read, and their device copies.
 
-Pure host code below `ops`: PIL's fixed-point bicubic coefficient tables, torchvision's normalisation table, the JPEG
-header and the encoder's tables, and what the PNG encoder builds (it reads no host-built table: its length codes are
+Pure host code below `ops`: PIL's fixed-point bicubic coefficient tables, torch's bilinear taps and weights, torchvision's
+normalisation table, the JPEG header and the encoder's tables, and what the PNG encoder builds (it reads no host-built table: its length codes are
 arithmetic, its CRC bitwise).  The `device_*` functions put them on a device under the one rule of `_consts`.
 `pipeline.image_output` re-exports the names for the callers that know them from there.
 """
@@ -216,6 +216,44 @@ def png_unit_lut():
     """torchvision's ToTensor on every byte value, with torch's own float32 division: (256,) float32 on the host,
     lut[b] = float32(b) / 255 — what the image-mode ORS condition is made of (ops.png_condition)."""
     return torch.arange(256).float().div(255).contiguous()
+
+
+BILINEAR_MAX = 1 << 14                 # sizes up to which bilinear_tables' float64 steps are exact (below)
+_BILINEAR = {}                         # (in, out) -> (taps int32 (out, 2), weights float32 (out, 2))
+
+
+def bilinear_tables(in_size, out_size):
+    """One axis of `F.interpolate(mode="bilinear", align_corners=False)` without antialias, in float32 as torch's CPU
+    kernel computes it: -> (taps int32 (out_size, 2) = [i0, i1], weights float32 (out_size, 2) = [l0, l1]); output d is
+    `l0 * x[i0] + l1 * x[i1]`.  scale = float32(in) / float32(out); src = fma(scale, float32(d) + 0.5, -0.5), negative
+    -> 0; i0 = int(src), i1 = i0 + (i0 < in - 1); l1 = clamp(src - i0, 0, 1), l0 = 1 - l1.  The fused multiply-add is
+    taken in float64 and rounded once: for sizes up to BILINEAR_MAX the product of the 24-bit scale and d + 0.5 (15 bits)
+    and its sum with -0.5 both fit 53 bits, so float64 holds them exactly.  The unfused float32 form differs (by up to
+    4e-6 in the result at 225 -> 216) and is not what torch computes."""
+    import numpy as np
+    in_size, out_size = int(in_size), int(out_size)
+    if not (0 < in_size <= BILINEAR_MAX and 0 < out_size <= BILINEAR_MAX):
+        raise ValueError("sizes must be in 1..%d, got %d -> %d" % (BILINEAR_MAX, in_size, out_size))
+    key = (in_size, out_size)
+    if key not in _BILINEAR:
+        f32 = np.float32
+        scale = f32(in_size) / f32(out_size)
+        dst = np.arange(out_size, dtype=f32) + f32(0.5)
+        src = (np.float64(scale) * dst.astype(np.float64) - 0.5).astype(f32)
+        src = np.maximum(src, f32(0))
+        i0 = np.minimum(src.astype(np.int32), in_size - 1)
+        i1 = i0 + (i0 < in_size - 1)
+        l1 = np.clip(src - i0.astype(f32), f32(0), f32(1)).astype(f32)
+        l0 = (f32(1) - l1).astype(f32)
+        _BILINEAR[key] = (torch.from_numpy(np.stack([i0, i1], axis=1).astype(np.int32)),
+                          torch.from_numpy(np.stack([l0, l1], axis=1).astype(f32)))
+    return _BILINEAR[key]
+
+
+def device_bilinear_tables(in_size, out_size, device):
+    """bilinear_tables of one axis on `device` (_consts.device_const)."""
+    n, out = int(in_size), int(out_size)
+    return device_const(("bilinear", n, out), device, lambda: bilinear_tables(n, out))
 
 
 def png_capacity(h, w, channels=3):

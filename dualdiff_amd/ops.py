@@ -18,8 +18,8 @@ from ._consts import device_const
 from ._native import DD_BF16, DD_EPI_GEGLU, DD_EPI_NONE, DD_EPI_SILU, DD_F16, AttnDesc, Gemm8Desc, GemmDesc, XAttnDesc
 from ._timer import KernelTimer, _stream, set_timer  # noqa: F401
 from ._workspace import workspace, workspace_owner  # noqa: F401
-from .image_tables import (PNG_FILE_FIXED, _image_lut, _image_mean_std, device_jpeg_tables, device_tables,  # noqa: F401
-                           image_norm_lut, jpeg_header, png_capacity, png_unit_lut)
+from .image_tables import (BILINEAR_MAX, PNG_FILE_FIXED, _image_lut, _image_mean_std, device_bilinear_tables,  # noqa: F401
+                           device_jpeg_tables, device_tables, image_norm_lut, jpeg_header, png_capacity, png_unit_lut)
 from .tuning import (CHALLENGE_TILES, TUNE_TABLE_PATH, forget_tuned, load_tuned, save_tuned,  # noqa: F401
                      tune_candidates, tuned_table)
 
@@ -736,7 +736,61 @@ def png_condition(frames, views=6, top=0, left=0, size=None, out=None):
     return out
 
 
-BOX_POINT_MODES = {"all-xyz": 0, "cxyz": 1}      # dataset/utils.py:222-226; points per box 8 / 4
+def png_condition_resized(frames, views=6, pad_top=0, resize=None, top=0, left=0, size=None, out=None):
+    """png_condition with `crop_drivewm`'s pad and resize in front of the crop (dd_png_condition_resize; dataset/utils.py:
+    355-358, 374-388): every view of the uint8 frames (b, H, W, 3) gets `pad_top` zero rows on top, is resized to resize =
+    (rh, rw) as `F.interpolate(mode="bilinear", align_corners=False)` resizes it, without antialias and per view, and is
+    cropped to rows top .. top + oh, columns left .. left + ow of the RESIZED view -> float32 (b, 3, oh, views * ow).
+    resize: None keeps (H + pad_top, W / views), and that size gives png_condition's bits.  size: (oh, ow), None for the
+    rest of the resized view.  The taps and weights of both axes are built on the host in float32
+    (image_tables.bilinear_tables) and are device constants under the rule of _consts, as the byte / 255 table is."""
+    what = "png_condition_resized"
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
+        raise ValueError("%s takes a (b, H, W, 3) frame batch, got %s" % (what, tuple(frames.shape)))
+    if frames.dtype != torch.uint8:
+        raise ValueError("%s takes uint8 frames, got %s" % (what, frames.dtype))
+    if not frames.is_contiguous():
+        raise ValueError("%s takes a contiguous NHWC tensor" % what)
+    b, h, w = frames.shape[0], frames.shape[1], frames.shape[2]
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in (views, pad_top, top, left)) or views <= 0 or w % views:
+        raise ValueError("%s: views must be a positive int that divides the width %d, pad_top, top and left ints; got %r, %r, "
+                         "%r, %r" % (what, w, views, pad_top, top, left))
+    if pad_top < 0:
+        raise ValueError("%s: pad_top must not be negative, got %d" % (what, pad_top))
+    pw = w // views
+    try:
+        rh, rw = (h + pad_top, pw) if resize is None else (int(v) for v in resize)
+    except (TypeError, ValueError):
+        raise ValueError("resize must be (h, w), got %r" % (resize,))
+    if not (0 < rh <= BILINEAR_MAX and 0 < rw <= BILINEAR_MAX and h + pad_top <= BILINEAR_MAX and pw <= BILINEAR_MAX):
+        raise ValueError("%s: a view of %d x %d resized to %d x %d: sizes are 1..%d" % (what, h + pad_top, pw, rh, rw, BILINEAR_MAX))
+    try:
+        oh, ow = (rh - top, rw - left) if size is None else (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError("size must be (h, w), got %r" % (size,))
+    if not (0 <= top and 0 <= left and 0 < oh and 0 < ow and top + oh <= rh and left + ow <= rw):
+        raise ValueError("%s: the crop top %d, left %d, size %d x %d leaves the resized %d x %d view" % (what, top, left, oh, ow, rh, rw))
+    shape = (b, 3, oh, views * ow)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=frames.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError("%s: out must be a contiguous float32 %s tensor" % (what, shape))
+    _need_gpu(frames, out)
+    if out.data_ptr() % 16:
+        raise ValueError("%s: out must start on a 16-byte boundary" % what)
+    _forget_derived(out)
+    lib = _native.load()
+    lut = device_const("png_unit_lut", frames.device, png_unit_lut)
+    row_taps, row_weights = device_bilinear_tables(h + pad_top, rh, frames.device)
+    col_taps, col_weights = device_bilinear_tables(pw, rw, frames.device)
+    _timer.launch(what, lib.dd_png_condition_resize, _ptr(frames), _ptr(out), _ptr(lut), _ptr(row_taps), _ptr(row_weights),
+                  _ptr(col_taps), _ptr(col_weights), b, h, w, views, pad_top, rh, rw, top, left, oh, ow, _stream(),
+                  # four bytes read per float written; they share cache lines
+                  book=lambda: ("dd_png_condition_resize_kernel", 0.0, float(out.numel() * 4 + frames.numel())))
+    return out
+
+
+BOX_POINT_MODES = {"all-xyz": 0, "cxyz": 1}     # dataset/utils.py:222-226; points per box 8 / 4
 BOX_FILTERS = {"all": 0, "positive_z": 1, "canvas": 2}
 
 

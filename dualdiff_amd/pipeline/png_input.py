@@ -3,7 +3,8 @@
 With `use_occ_3d=False` (the DualDiff default for both ControlNet branches) the ORS condition of a sample is one .png, an
 RGBA panorama of the six views, that the reference opens with PIL on the host (`OccFolderSetWrapper(mode='image')`,
 magicdrive/dataset/dataset_wrapper.py:62-81, misc/test_utils.py:218-222: `ToTensor()(Image.open(f).convert("RGB"))`) and
-that `collate_fn` stacks and, for 256 x 704, crops per view (dataset/utils.py:348-408).  Here the host walks each file's
+that `collate_fn` stacks and, for 256 x 704, crops per view and, for 192 x 384, pads, resizes and crops per view
+(dataset/utils.py:348-408; ResizedOccCondition, one launch of `ops.png_condition_resized`).  Here the host walks each file's
 chunks — framing and checksums, not the compressed bytes — and the device does the rest in one call per batch
 (`ops.png_decode_u8`): inflate, the Adler-32, the five row filters and the conversion to RGB, so the frames equal
 `np.asarray(Image.open(f).convert("RGB"))` byte for byte.  The files `encode_png` / `save_png` write come back the same
@@ -11,7 +12,8 @@ way, their 16 KiB chunks decoded side by side where the device can verify that t
 
     frames = load_png(paths)                              # (b, n, H, W, 3) uint8 on the GPU; paths nested (b, n), or flat
     frames = decode_png(files)                            # ... from `bytes`
-    cond = OccCondition.from_config(cfg)(files)           # (b, 3, h, 6 w) float32: `controlnet_cond` of the default mode
+    cond = occ_condition_from_config(cfg)(files)          # (b, 3, h, 6 w) float32: `controlnet_cond` of the default mode,
+                                                          # for every image_size the reference configures
 
 What is built is PNG_INPUT_MODES; any other file is turned down on the host with a ValueError that names the frame and
 what was found, before anything is uploaded, and is the caller's to decode (with PIL).  This module does not import PIL.
@@ -245,7 +247,8 @@ class OccCondition:
             return cls(in_hw=(432, 768), out_hw=(256, 704))  # crop_hd, utils.py:348-372
         if size == [192, 384]:
             raise NotImplementedError("image_size [192, 384] takes crop_drivewm (dataset/utils.py:374-388), which resizes "
-                                      "with torchvision and is not built")
+                                      "with torchvision and is not built into OccCondition: occ_condition_from_config(cfg) "
+                                      "returns ResizedOccCondition.drivewm() for it")
         raise ValueError("image_size %r: the image-mode ORS condition is defined for [224, 400], [432, 768] and [256, 704]"
                          % (size,))
 
@@ -269,3 +272,71 @@ class OccCondition:
             raise ValueError("OccCondition takes a flat list of files or (b, H, W, 3) frames, got %s" % (tuple(frames.shape),))
         top, left, oh, ow = self.crop(frames.shape[1], frames.shape[2])
         return O.png_condition(frames, views=self.views, top=top, left=left, size=(oh, ow))
+
+
+class ResizedOccCondition:
+    """The collate step of the image-mode ORS condition where it resizes (`crop_drivewm`, dataset/utils.py:355-358,
+    374-388, for image_size [192, 384]): each of the `views` views of in_hw = (H, W / views) gets `pad_top` zero rows on
+    top, is resized to resize_hw with `transforms.Resize` as the reference's torchvision 0.11.3 applies it to a float
+    tensor — bilinear at half-pixel centres, no antialias, per view — and is cropped to out_hw as `hd_crop` does: the top
+    rows and (resize_hw[1] - out_hw[1]) // 2 columns on each side dropped.  Same call as OccCondition: float32 (b, 3, h,
+    views * w) on the device.  antialias=True — what torchvision from 0.17 on does to a tensor by default — is not built."""
+
+    def __init__(self, views=6, in_hw=None, pad_top=0, resize_hw=None, out_hw=None, antialias=False):
+        if antialias:
+            raise ValueError("antialias=True is not built: crop_drivewm resizes with torchvision 0.11.3, whose Resize does not "
+                             "antialias a tensor (torchvision >= 0.17 does by default and gives another condition)")
+        if isinstance(views, bool) or not isinstance(views, int) or views <= 0:
+            raise ValueError("views must be a positive int, got %r" % (views,))
+        if isinstance(pad_top, bool) or not isinstance(pad_top, int) or pad_top < 0:
+            raise ValueError("pad_top must be an int >= 0, got %r" % (pad_top,))
+        if in_hw is None or resize_hw is None or out_hw is None:
+            raise ValueError("in_hw, resize_hw and out_hw are (h, w) each (ResizedOccCondition.drivewm() has the reference's)")
+        try:
+            (ih, iw), (rh, rw), (oh, ow) = ([int(v) for v in hw] for hw in (in_hw, resize_hw, out_hw))
+        except (TypeError, ValueError):
+            raise ValueError("in_hw, resize_hw and out_hw are (h, w) each, got %r, %r, %r" % (in_hw, resize_hw, out_hw))
+        if ih <= 0 or iw <= 0 or rh <= 0 or rw <= 0:
+            raise ValueError("in_hw %r and resize_hw %r must be positive" % (tuple(in_hw), tuple(resize_hw)))
+        if not (0 < oh <= rh and 0 < ow <= rw) or (rw - ow) % 2:
+            raise ValueError("out_hw %r must fit resize_hw %r, the width difference even (hd_crop asserts the result's shape)"
+                             % (tuple(out_hw), tuple(resize_hw)))
+        self.views, self.pad_top, self.in_hw, self.resize_hw, self.out_hw = views, pad_top, (ih, iw), (rh, rw), (oh, ow)
+
+    @classmethod
+    def drivewm(cls):
+        """224 x 400 -pad_top-> 225 x 400 -resize-> 216 x 384 -top crop-> 192 x 384 (utils.py:375)"""
+        return cls(views=6, in_hw=(224, 400), pad_top=1, resize_hw=(216, 384), out_hw=(192, 384))
+
+    def crop(self, h, w):
+        """(top, left, oh, ow) in the resized view, for frames of h x w"""
+        if w % self.views:
+            raise ValueError("a panorama of %d views has a width that %d divides, got %d" % (self.views, self.views, w))
+        if (h, w // self.views) != self.in_hw:
+            raise ValueError("the panoramas are %d x %d x %d, the resize is defined for %d x %d x %d"
+                             % (h, self.views, w // self.views, self.in_hw[0], self.views, self.in_hw[1]))
+        return (self.resize_hw[0] - self.out_hw[0], (self.resize_hw[1] - self.out_hw[1]) // 2, self.out_hw[0], self.out_hw[1])
+
+    @torch.no_grad()
+    def __call__(self, files_or_frames, device="cuda"):
+        """A flat list of b .png files (`bytes`), or uint8 frames (b, H, W, 3) already on the device -> (b, 3, h, views *
+        w) float32: `torch.stack([crop_drivewm(ToTensor()(Image.open(f).convert("RGB"))) ...])` in the arithmetic of
+        INTEGRATION.md 4o."""
+        frames = files_or_frames if isinstance(files_or_frames, torch.Tensor) else decode_png(files_or_frames, device=device)
+        if frames.dim() != 4:
+            raise ValueError("ResizedOccCondition takes a flat list of files or (b, H, W, 3) frames, got %s"
+                             % (tuple(frames.shape),))
+        top, left, oh, ow = self.crop(frames.shape[1], frames.shape[2])
+        return O.png_condition_resized(frames, views=self.views, pad_top=self.pad_top, resize=self.resize_hw, top=top,
+                                       left=left, size=(oh, ow))
+
+
+def occ_condition_from_config(cfg):
+    """cfg.dataset.image_size (attributes or mappings) -> what collate_fn does to the image-mode ORS condition for it
+    (dataset/utils.py:390-408): an OccCondition for [224, 400], [432, 768] and [256, 704], ResizedOccCondition.drivewm()
+    for [192, 384]; ValueError for any other size."""
+    dataset = cfg["dataset"] if isinstance(cfg, dict) else cfg.dataset
+    size = [int(v) for v in (dataset["image_size"] if isinstance(dataset, dict) else dataset.image_size)]
+    if size == [192, 384]:
+        return ResizedOccCondition.drivewm()
+    return OccCondition.from_config(cfg)

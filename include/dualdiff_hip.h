@@ -691,6 +691,26 @@ int dd_jpeg_decode_u8(const uint8_t* scan, int64_t scan_bytes, const int32_t* of
  * rows top .. top + oh and, per view, columns left .. left + ow (crop_hd: top 176, left 32, 256 x 704 of 432 x 768).
  * lut: float32 [256] (device): byte / 255, built by the caller.  DD_ERR_BAD_ARG: a NULL pointer, a size <= 0, top or
  * left < 0, w no multiple of views, a crop that leaves the view, a misaligned out / lut.
+ *
+ * dd_png_condition_resize: the same step for image_size [192, 384], `crop_drivewm` (dataset/utils.py:355-358 pad_top,
+ * :374-388, called at :398-403), one launch, no host synchronisation: every view of uint8 frames [b][h][w][3] gets
+ * `pad_top` zero rows on top, is resized to rh x rw as torchvision 0.11.3's `transforms.Resize((216, 384))` resizes a float
+ * tensor — `F.interpolate(mode="bilinear", align_corners=False)`, no antialias, PER VIEW: the clamp at a view's last column
+ * and the rounding of the coordinates are the view's own — and cropped to rows top .. top + oh, columns left .. left + ow
+ * (hd_crop: top 24, left 0, 192 x 384 of 216 x 384); out float32 [b][3][oh][views * ow], 16-byte aligned.
+ * row_taps / col_taps: int32 [rh][2] / [rw][2] (device), per resized row / column its two source positions (i0, i1) in the
+ * PADDED view, [0, h + pad_top) / [0, w / views); clamped to that range whatever they hold.  row_weights / col_weights:
+ * float32 [rh][2] / [rw][2], (l0, l1).  The caller builds them in float32 (image_tables.bilinear_tables):
+ *   scale = float(in) / float(out);  src = fmaf(scale, float(dst) + 0.5f, -0.5f), src < 0 -> 0;  i0 = (int)src,
+ *   i1 = i0 + (i0 < in - 1);  l1 = clamp(src - i0, 0, 1), l0 = 1 - l1.
+ * With A, B the values lut[byte] (0.0f in a padded row) at (i0 row, i0 / i1 column) and C, D those of row i1:
+ *   t = fmaf(bl0, A, bl1 * B);  u = fmaf(bl0, C, bl1 * D);  out = fmaf(al0, t, al1 * u),
+ * every product and every fused multiply-add rounded once to float32 — the form that torch's multi-threaded CPU kernel
+ * takes at the reference's geometry; torch's single-threaded one differs from it in the last place.  An identity resize
+ * (rh = h + pad_top, rw = w / views) has l1 = 0 everywhere and returns dd_png_condition's bits.
+ * DD_ERR_BAD_ARG, before any runtime call: a NULL pointer, a size <= 0, pad_top / top / left < 0, w no multiple of views, a
+ * crop that leaves the resized view, an out that is not 16-byte aligned, a misaligned table.  A frame of 2^31 bytes or
+ * more, or a batch of more than 2^40: DD_ERR_UNSUPPORTED.
  * ------------------------------------------------------------------------- */
 #define DD_PNG_TRUNCATED 1
 #define DD_PNG_BAD_BLOCK 2
@@ -709,6 +729,10 @@ int dd_png_decode_u8(const uint8_t* streams, int64_t streams_bytes, const int32_
                      int32_t* status, int32_t* paths, void* workspace, int64_t workspace_bytes, dd_stream_t stream);
 int dd_png_condition(const uint8_t* frames, float* out, const float* lut, int32_t b, int32_t h, int32_t w, int32_t views,
                      int32_t top, int32_t left, int32_t oh, int32_t ow, dd_stream_t stream);
+int dd_png_condition_resize(const uint8_t* frames, float* out, const float* lut, const int32_t* row_taps,
+                            const float* row_weights, const int32_t* col_taps, const float* col_weights, int32_t b, int32_t h,
+                            int32_t w, int32_t views, int32_t pad_top, int32_t rh, int32_t rw, int32_t top, int32_t left,
+                            int32_t oh, int32_t ow, dd_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * Map output (csrc/map.hip): the picture the reference's `visualize_map` makes of a sample's BEV map
