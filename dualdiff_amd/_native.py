@@ -204,6 +204,15 @@ SIGNATURES = {
                                           c_int64, c_int32, c_void_p]),
     "dd_given_views_noise": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int64,
                                        c_int64, c_int32, c_void_p]),
+    "dd_conv2d_nhwc": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32,
+                                 c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                 c_int32, c_void_p]),
+    "dd_conv2d_kernel_name": (c_char_p, [c_int64, c_int32, c_int32, c_int32]),
+    "dd_pool3x3_nhwc": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                  c_int32, c_void_p]),
+    "dd_global_avgpool_nhwc": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "dd_inception_input": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                     c_int32, c_int32, c_int32, c_void_p]),
 }
 
 ABI_VERSION = 4

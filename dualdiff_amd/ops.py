@@ -1699,3 +1699,128 @@ def gemm_kernel_name(rows, n, k, dtype=torch.bfloat16, conv=False, cin=0, hw=(0,
         d.conv = 1
         d.cin = cin; d.hin = d.hv = d.hout = hw[0]; d.win = d.wv = d.wout = hw[1]; d.stride = 1
     return lib.dd_gemm_kernel_name(ctypes.byref(d)).decode()
+
+
+# ---- FID feature extractor (csrc/conv2d.hip) ----------------------------------------------------------------------------
+CONV2D_TILES = {None: 0, "64x64": 1, "128x64": 2}
+POOL3X3_MODES = {"max_s2": 0, "max_s1": 1, "avg_s1": 2}     # avg: count_include_pad=False
+
+
+def conv2d_out_hw(h, w, kh, kw, stride, pad):
+    """Output size of conv2d: pad = (pad_h, pad_w)."""
+    return (h + 2 * pad[0] - kh) // stride + 1, (w + 2 * pad[1] - kw) // stride + 1
+
+
+def _slice_out(out, rows, cols, c_off, dtype, device, what):
+    """The (rows, ldc) tensor a slice-writing kernel stores into and its column offset: a fresh (rows, cols) one, or the
+    caller's, of which columns c_off .. c_off + cols - 1 are written and every other one is left alone."""
+    if out is None:
+        if c_off:
+            raise ValueError("%s: c_off needs out" % what)
+        return torch.empty((rows, cols), dtype=dtype, device=device)
+    if out.dtype != dtype:
+        raise TypeError("%s: out must be %s" % (what, dtype))
+    _rows2d(out)
+    if out.shape[0] != rows or c_off < 0 or c_off + cols > out.shape[1]:
+        raise ValueError("%s: out %s cannot hold %d rows x columns %d..%d" % (what, tuple(out.shape), rows, c_off,
+                                                                               c_off + cols))
+    _forget_derived(out)
+    return out
+
+
+def conv2d(x, w, scale, shift, m, h, wd, kh, kw, *, stride=1, pad=(0, 0), relu=True, out=None, c_off=0, tile=None):
+    """General NHWC convolution with the eval-mode BatchNorm + ReLU epilogue (dd_conv2d_nhwc): x (m*h*wd, cin) dense, w
+    (cout, kh*kw*cin) packed [cout][ky][kx][cin], scale / shift fp32 (cout,) ->
+    relu(conv * scale + shift) in columns c_off .. c_off + cout - 1 of `out` (rows m*hout*wout; a fresh (rows, cout)
+    tensor when None).  kh, kw in 1..7, stride 1 / 2, pad = (pad_h, pad_w) <= (kh // 2, kw // 2), cin % 8 == 0,
+    cout % 4 == 0."""
+    lib = _native.load()
+    _need_gpu(x, w, scale, shift, out)
+    cin, cout = x.shape[1], w.shape[0]
+    if x.shape[0] != m * h * wd or not x.is_contiguous():
+        raise ValueError("conv2d: x must be contiguous (m*h*wd, cin), got %s" % (tuple(x.shape),))
+    if w.dtype != x.dtype or w.shape[1] != kh * kw * cin or not w.is_contiguous():
+        raise ValueError("conv2d: w must be contiguous %s (cout, %d), got %s %s" % (x.dtype, kh * kw * cin, w.dtype,
+                                                                                    tuple(w.shape)))
+    for t in (scale, shift):
+        if t.dtype != torch.float32 or t.shape != (cout,) or not t.is_contiguous():
+            raise ValueError("conv2d: scale / shift must be contiguous fp32 (%d,)" % cout)
+    if tile not in CONV2D_TILES:
+        raise ValueError("conv2d: tile must be one of %s" % (sorted(k for k in CONV2D_TILES if k),))
+    pad_h, pad_w = (int(v) for v in pad)
+    hout, wout = conv2d_out_hw(h, wd, kh, kw, stride, (pad_h, pad_w))
+    if hout <= 0 or wout <= 0:
+        raise ValueError("conv2d: a %d x %d image has no output under a %d x %d kernel with pad %s" % (h, wd, kh, kw, pad))
+    rows = m * hout * wout
+    out = _slice_out(out, rows, cout, c_off, x.dtype, x.device, "conv2d")
+    _timer.launch("conv2d", lib.dd_conv2d_nhwc, _ptr(x), _ptr(w), _ptr(scale), _ptr(shift), _ptr(out), out.stride(0),
+                  c_off, m, h, wd, cin, cout, kh, kw, stride, pad_h, pad_w, int(bool(relu)), CONV2D_TILES[tile], _dt(x),
+                  _stream(),
+                  book=lambda: (conv2d_kernel_name(rows, cout, x.dtype, tile)
+                                + (" conv %dx%dx%d" % (rows, cout, kh * kw * cin) if _timer._TIMER.shapes else ""),
+                                2.0 * rows * cout * kh * kw * cin,
+                                2.0 * (x.numel() + w.numel() + rows * cout)))
+    return out
+
+
+def conv2d_kernel_name(rows, cout, dtype=torch.float16, tile=None):
+    """Name of the kernel dd_conv2d_nhwc picks for a shape (profile matching)."""
+    return _native.load().dd_conv2d_kernel_name(rows, cout, CONV2D_TILES[tile], _dtype_code(dtype)).decode()
+
+
+def pool3x3(x, m, h, wd, mode, *, out=None, c_off=0):
+    """3 x 3 pooling of NHWC rows (dd_pool3x3_nhwc): x (m*h*wd, c) dense, c % 8 == 0; mode "max_s2" (stride 2, pad 0),
+    "max_s1" (stride 1, pad 1) or "avg_s1" (stride 1, pad 1, count_include_pad=False) -> columns c_off .. c_off + c - 1
+    of `out`."""
+    lib = _native.load()
+    _need_gpu(x, out)
+    if mode not in POOL3X3_MODES:
+        raise ValueError("pool3x3: mode must be one of %s, got %r" % (", ".join(sorted(POOL3X3_MODES)), mode))
+    c = x.shape[1]
+    if x.shape[0] != m * h * wd or not x.is_contiguous():
+        raise ValueError("pool3x3: x must be contiguous (m*h*wd, c), got %s" % (tuple(x.shape),))
+    hout, wout = ((h - 3) // 2 + 1, (wd - 3) // 2 + 1) if mode == "max_s2" else (h, wd)
+    if hout <= 0 or wout <= 0:
+        raise ValueError("pool3x3: a %d x %d image has no 3 x 3 stride-2 output" % (h, wd))
+    rows = m * hout * wout
+    out = _slice_out(out, rows, c, c_off, x.dtype, x.device, "pool3x3")
+    _timer.launch("pool3x3", lib.dd_pool3x3_nhwc, _ptr(x), _ptr(out), out.stride(0), c_off, m, h, wd, c,
+                  POOL3X3_MODES[mode], _dt(x), _stream(),
+                  book=lambda: ("dd_pool3x3_kernel" + (" %s %dx%d" % (mode, rows, c) if _timer._TIMER.shapes else ""), 0.0,
+                                2.0 * (x.numel() + rows * c)))
+    return out
+
+
+def global_avgpool(x, m, hw, out=None):
+    """x (m*hw, c) NHWC rows -> fp32 (m, c) means over the hw pixels, summed in fp32 (dd_global_avgpool_nhwc)."""
+    lib = _native.load()
+    _need_gpu(x, out)
+    c = x.shape[1]
+    if x.shape[0] != m * hw or not x.is_contiguous():
+        raise ValueError("global_avgpool: x must be contiguous (m*hw, c), got %s" % (tuple(x.shape),))
+    out = _out_or_new(out, (m, c), torch.float32, x.device, "global_avgpool")
+    if tuple(out.shape) != (m, c) or not out.is_contiguous():
+        raise ValueError("global_avgpool: out must be contiguous (%d, %d)" % (m, c))
+    _timer.launch("global_avgpool", lib.dd_global_avgpool_nhwc, _ptr(x), _ptr(out), m, hw, c, _dt(x), _stream(),
+                  book=lambda: ("dd_global_avgpool_kernel", 0.0, 2.0 * x.numel() + 4.0 * m * c))
+    return out
+
+
+def inception_input(x, size=(299, 299), *, resize=True, normalize=True, dtype=torch.float16, c_pad=8, out=None):
+    """(m, 3, h, w) images in [0, 1] (fp16 / bf16 / fp32) -> (m*oh*ow, c_pad) NHWC rows of `dtype`:
+    F.interpolate(size, mode="bilinear", align_corners=False) unless resize is false, then 2 x - 1 unless normalize is
+    false; channels 3 .. c_pad - 1 are zero (dd_inception_input)."""
+    m, h, w = _image_arg(x, "inception_input")
+    oh, ow = (int(size[0]), int(size[1])) if resize else (h, w)
+    if oh <= 0 or ow <= 0:
+        raise ValueError("inception_input: size must be positive, got %r" % (size,))
+    _need_gpu(x, out)
+    lib = _native.load()
+    out = _out_or_new(out, (m * oh * ow, c_pad), dtype, x.device, "inception_input")
+    if tuple(out.shape) != (m * oh * ow, c_pad) or not out.is_contiguous():
+        raise ValueError("inception_input: out must be contiguous (%d, %d)" % (m * oh * ow, c_pad))
+    _timer.launch("inception_input", lib.dd_inception_input, _ptr(x), _ptr(out), m, h, w, oh, ow, c_pad,
+                  int(bool(resize)), int(bool(normalize)), _FDT[x.dtype], _dtype_code(dtype), _stream(),
+                  book=lambda: ("dd_inception_input_kernel", 0.0,
+                                float(x.numel() * x.element_size() + out.numel() * out.element_size())))
+    return out

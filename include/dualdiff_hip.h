@@ -441,6 +441,55 @@ int dd_vae_posterior(const void* moments, const float* wq, const float* bq, cons
                      int32_t m, int32_t h, int32_t w, float scale, int32_t out_f32, int32_t dtype, dd_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * FID feature extractor (csrc/conv2d.hip): the InceptionV3 of the reference's evaluation step, tools/fid_score.py:93-156
+ * (get_activations) -> magicdrive/misc/inception.py (pytorch-fid's FID network).  Backward-compatible additions to ABI 4.
+ *
+ * dd_conv2d_nhwc: every BasicConv2d of that network (inception.py: the torchvision Inception blocks it instantiates at
+ * :84-124 and the FID variants at :224-341; each is conv without bias -> BatchNorm2d(eps = 1e-3) in eval -> ReLU):
+ *   out[p, c_off + n] = relu( scale[n] * sum_{ky,kx,ci} x[img, oy s - pad_h + ky, ox s - pad_w + kx, ci] w[n, ky, kx, ci]
+ *                             + shift[n] )
+ * x: T NHWC [m][h][wd][cin], dense, 16-byte aligned, cin % 8 == 0 (the stem's 3 channels are zero-padded to 8 by
+ * dd_inception_input and by the weight packing); w: T [cout][kh][kw][cin], 16-byte aligned; cout % 4 == 0;
+ * scale / shift: fp32 [cout] (gamma / sqrt(var + eps) and beta - mean * that: BatchNorm stays in fp32, it is NOT folded
+ * into the 16-bit weights); accumulation in fp32; relu: 0 / 1.
+ * kh, kw in 1..7; stride 1 or 2 (both axes); 0 <= pad_h <= kh / 2, 0 <= pad_w <= kw / 2; taps outside the image read
+ * zero; hout = (h + 2 pad_h - kh) / stride + 1 (likewise wout), p = (img * hout + oy) * wout + ox.
+ * out: T, row stride ldc >= c_off + cout elements, ldc % 4 == 0, c_off % 4 == 0, 8-byte aligned: a branch writes its
+ * slice of the block's concatenated tensor (the torch.cat of inception.py:246, 274, 307, 341); other columns are untouched.
+ * tile: 0 = chosen from the shape, 1 = 64 pixels x 64 channels, 2 = 128 x 64 per workgroup.
+ * Shapes outside these rules are DD_ERR_UNSUPPORTED, bad pointers / sizes / a slice that does not fit ldc DD_ERR_BAD_ARG.
+ * storage_type (here and below): DD_F16 / DD_BF16, the element type T of activations and weights; any other value is
+ * DD_ERR_BAD_ARG (tests/test_fid_cpu.py). */
+int dd_conv2d_nhwc(const void* x, const void* w, const float* scale, const float* shift, void* out, int64_t ldc,
+                   int32_t c_off, int32_t m, int32_t h, int32_t wd, int32_t cin, int32_t cout, int32_t kh, int32_t kw,
+                   int32_t stride, int32_t pad_h, int32_t pad_w, int32_t relu, int32_t tile, int32_t storage_type,
+                   dd_stream_t stream);
+/* Name of the kernel instantiation dd_conv2d_nhwc launches for rows = m * hout * wout output pixels, for profile
+ * matching; "" for arguments it would reject. */
+const char* dd_conv2d_kernel_name(int64_t rows, int32_t cout, int32_t tile, int32_t storage_type);
+
+/* The 3 x 3 pools of that network, NHWC, c % 8 == 0, x dense [m][h][wd][c], out as dd_conv2d_nhwc's (ldc % 8 == 0,
+ * c_off % 8 == 0, 16-byte aligned):
+ *   mode 0: max, stride 2, pad 0   (F.max_pool2d(x, kernel_size=3, stride=2): inception.py:89, 98 and the grid
+ *                                   reductions Mixed_6a / Mixed_7a)
+ *   mode 1: max, stride 1, pad 1   (FIDInceptionE_2, :333-338; only in-image taps take part)
+ *   mode 2: average, stride 1, pad 1, divided by the number of in-image taps (count_include_pad=False, the FID patch
+ *           at :241-242, 269-270, 302-303) */
+int dd_pool3x3_nhwc(const void* x, void* out, int64_t ldc, int32_t c_off, int32_t m, int32_t h, int32_t wd, int32_t c,
+                    int32_t mode, int32_t storage_type, dd_stream_t stream);
+/* AdaptiveAvgPool2d(1) (inception.py:122) / get_activations' adaptive_avg_pool2d (tools/fid_score.py:147-148):
+ * x T [m][hw][c] -> out fp32 [m][c], summed in fp32 in pixel order. */
+int dd_global_avgpool_nhwc(const void* x, float* out, int32_t m, int32_t hw, int32_t c, int32_t storage_type,
+                           dd_stream_t stream);
+/* The head of forward(inp) (inception.py:146-153): x [m][3][h][wd] in [0, 1], in_type DD_F16 / DD_BF16 / 2 (fp32)
+ * -> F.interpolate(size=(oh, ow), mode='bilinear', align_corners=False) (no antialiasing; resize = 0 skips it and needs
+ * oh == h, ow == wd) -> 2 x - 1 (normalize = 0 skips it) -> out T NHWC [m][oh][ow][c_pad], channels 3 .. c_pad - 1
+ * zero, c_pad % 8 == 0. */
+int dd_inception_input(const void* x, void* out, int32_t m, int32_t h, int32_t wd, int32_t oh, int32_t ow,
+                       int32_t c_pad, int32_t resize, int32_t normalize, int32_t in_type, int32_t storage_type,
+                       dd_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Image output (csrc/image.hip): what the reference does to the decoded images before it saves them — the host copy
  * and diffusers' numpy_to_pil, `(images * 255).round().astype("uint8")` (pipeline/pipeline_bev_controlnet.py:112,540,
  * numpy_to_pil_double :72-80), then per view torchvision's Resize(cfg.fid.resize, BICUBIC) and Pad(cfg.fid.padding) on
