@@ -22,7 +22,9 @@ SOURCES = ["gemm23.hip", "gemm2_conv.hip", "attention.hip", "gemm1.hip", "conv3s
            "norm.hip", "elementwise.hip", "tokens.hip", "xattn.hip", "clip.hip", "gemm8.hip", "vae.hip", "image.hip", "boxes.hip", "jpeg.hip", "jpeg_decode.hip", "png.hip", "png_decode.hip", "map.hip", "box_overlay.hip", "gemm.hip",
            # last: the objects are linked in this order, and the FID kernels, which no denoising step launches, stay behind
            # the step's kernels instead of moving them
-           "conv2d.hip"]
+           "conv2d.hip",
+           # the ORS panorama render runs before the first step: behind everything, for the same reason
+           "ors_render.hip"]
 # per-source extra flags: the attention softmax lives on the MFMA results, so ask LLVM for the
 # VGPR-destination form of MFMA (gfx950 has a unified register file) instead of AGPR accumulators
 # that cost a v_accvgpr_read/write per touched element.

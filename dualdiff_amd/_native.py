@@ -145,6 +145,11 @@ SIGNATURES = {
     "dd_softmax_rows": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int64, c_int32, c_void_p]),
     "dd_ors_project": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                  c_float, c_int32, c_int32, c_int32, c_void_p]),
+    "dd_ors_first_hit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_int32,
+                                   c_void_p]),
+    "dd_ors_overlay_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                    c_void_p]),
     "dd_fourier_embed": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, POINTER(c_float), c_int32, c_int32,
                                    c_int32, c_int32, c_void_p]),
     "dd_conv3x3_small_cout": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,

@@ -2,6 +2,7 @@
 // 4-channel latent boundary, sinusoidal timestep embedding, conv_out (320->4) and the fused
 // CFG + DDIM update.  All vectorised to 16 B per lane where the shape allows.
 #include "dd_common.h"
+#include "ors_sample.h"
 
 namespace {
 
@@ -82,8 +83,8 @@ void dd_timestep_embedding_kernel(const float* t, T* out, int n, int dim, int fl
 }
 
 // ORS ray sampling: one thread per (camera, sample, pixel), pixel fastest (coalesced condition
-// writes).  fp32 with the reference's operation order and NO fma contraction: the result is a voxel
-// index, a last-bit difference could flip a class.
+// writes).  The coordinate-to-label chain is dd_ors_label (ors_sample.h), shared with the first-hit
+// render of ors_render.hip.
 template <typename T>
 __global__ __launch_bounds__(256)
 void dd_ors_project_kernel(const uint8_t* __restrict__ occ, const float* __restrict__ origin,
@@ -95,19 +96,7 @@ void dd_ors_project_kernel(const uint8_t* __restrict__ occ, const float* __restr
     const int64_t r = i / hw;
     const int s = (int)(r % samples);
     const int cam = (int)(r / samples);
-    const float t = __fmul_rn((float)s, step);
-    const float* o = origin + cam * 3;
-    const float* d = dir + ((int64_t)cam * hw + pix) * 3;
-    float g[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) g[a] = __fdiv_rn(__fadd_rn(o[a], __fmul_rn(t, d[a])), 40.0f);
-    const float gz = __fsub_rn(__fdiv_rn(__fmul_rn(g[2], 40.0f), 3.2f), 0.6875f);
-    auto idx = [](float c, float size) -> int {       // grid_sample nearest, align_corners = False
-      return (int)rintf(__fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(c, 1.0f), size), 1.0f), 2.0f));
-    };
-    const int ix = idx(g[0], 200.0f), iy = idx(g[1], 200.0f), iz = idx(gz, 16.0f);
-    int lab = 17;
-    if (ix >= 0 && ix < 200 && iy >= 0 && iy < 200 && iz >= 0 && iz < 16) lab = occ[(ix * 200 + iy) * 16 + iz];
+    const int lab = dd_ors_label(occ, origin + cam * 3, dir + ((int64_t)cam * hw + pix) * 3, s, step);
     if (labels) labels[((int64_t)cam * hw + pix) * samples + s] = (uint8_t)lab;
     if (cond) {
       int c = lab;

@@ -12,6 +12,10 @@ What stays on the host: the 6 x h x w ray table (K^-1, R, normalisation — 8400
 same torch fp32 calls as the reference so that the sampled coordinates are the reference's bit for bit,
 and cached per camera rig (nuScenes calibrations repeat across the samples of a log).
 
+`render_volume` / `render` make the OTHER ORS condition from the same rays: the image-mode panorama (first occupied class
+per ray, Occ3D palette, views side by side; occ3d_proj.py:156-198) in one launch of `dd_ors_first_hit` per batch —
+pipeline/occ_render.py is its user-facing form.
+
 Data access is injected rather than hard-wired: `camera_data[token][cam]` holds 'intrinsic' plus either
 'rotation_matrix' or 'rotation' (w, x, y, z quaternion) and 'translation'; `occ_loader(token)` returns
 the 200 x 200 x 16 class volume.  `from_reference_files` reads the reference's own pickles / labels.npz
@@ -26,6 +30,10 @@ import torch
 from .. import ops as O
 
 CAMERAS = ("CAM_FRONT_LEFT", "CAM_FRONT", "CAM_FRONT_RIGHT", "CAM_BACK_RIGHT", "CAM_BACK", "CAM_BACK_LEFT")
+# the Occ3D palette, class -> (r, g, b): colors_map[:, :3] of occ3d_proj.py:171-191
+OCC_COLORS = ((0, 0, 0), (255, 120, 50), (255, 192, 203), (255, 255, 0), (0, 150, 245), (0, 255, 255), (255, 127, 0),
+              (255, 0, 0), (255, 240, 150), (135, 60, 0), (160, 32, 240), (255, 0, 255), (139, 137, 137), (75, 0, 75),
+              (150, 240, 80), (230, 230, 250), (0, 175, 0), (0, 0, 0))
 
 
 def quaternion_rotation_matrix(q):
@@ -83,10 +91,14 @@ class OccupancyRay:
         m[:3, 3] = np.asarray(cam["translation"], dtype=np.float64)
         return torch.tensor(np.asarray(cam["intrinsic"]), dtype=torch.float32), torch.from_numpy(m).to(torch.float32)
 
+    @staticmethod
+    def _rig_key(intrinsics, extrinsics):
+        return (tuple(np.asarray(k, dtype=np.float32).tobytes() for k in intrinsics),
+                tuple(np.asarray(e, dtype=np.float32).tobytes() for e in extrinsics))
+
     def rays(self, intrinsics, extrinsics):
         """(origin (n, 3), direction (n, h*w, 3)) fp32 on self.device for a rig, cached by value."""
-        key = (tuple(np.asarray(k, dtype=np.float32).tobytes() for k in intrinsics),
-               tuple(np.asarray(e, dtype=np.float32).tobytes() for e in extrinsics))
+        key = self._rig_key(intrinsics, extrinsics)
         hit = self._ray_cache.get(key)
         if hit is not None:
             return hit
@@ -127,6 +139,63 @@ class OccupancyRay:
         _, cond = O.ors_project(self._volume(occ), origin, direction, self.sample_point, self.sample_step,
                                 want_labels=False, cond_dtype=dtype, keep_fg=use_fg, keep_bg=use_bg)
         return cond.view(len(intrinsics), self.sample_point, h, w)
+
+    # ---- the image-mode condition: first hit, palette, views side by side (occ3d_proj.py:156-198) ----
+    def _volumes(self, volumes):
+        if torch.is_tensor(volumes) and volumes.dim() == 4:
+            volumes = list(volumes)
+        vols = [torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v) for v in volumes]
+        if not vols:
+            raise ValueError("at least one occupancy volume is needed")
+        for v in vols:
+            if tuple(v.shape) != (200, 200, 16):
+                raise ValueError("occupancy volume must be 200 x 200 x 16, got %s" % (tuple(v.shape),))
+        where = {v.device for v in vols}
+        if len(where) > 1:
+            vols = [v.cpu() for v in vols]
+        return torch.stack([v.to(torch.uint8) for v in vols]).contiguous().to(self.device, non_blocking=True)
+
+    def render_batch(self, volumes, rigs, mode="bg", want_frames=True, want_classes=False, palette=None, **kw):
+        """b volumes and their b rigs ((intrinsics, extrinsics) each) in ONE launch of `ops.ors_first_hit`: the volumes
+        stacked, equal rigs found through the ray cache's key and their tables stored once.  -> (frames (b, h, n * w, 3)
+        uint8 | None, cls (b, n, h, w) uint8 | None)."""
+        occ = self._volumes(volumes)
+        rigs = list(rigs)
+        if len(rigs) != occ.shape[0]:
+            raise ValueError("%d volumes need %d rigs, got %d" % (occ.shape[0], occ.shape[0], len(rigs)))
+        index, tables, rig_of_sample = {}, [], []
+        for intrinsics, extrinsics in rigs:
+            if len(intrinsics) != len(extrinsics) or len(intrinsics) == 0:
+                raise ValueError("a rig is (intrinsics, extrinsics) with one matrix each per camera")
+            key = self._rig_key(intrinsics, extrinsics)
+            if key not in index:
+                index[key] = len(tables)
+                tables.append(self.rays(intrinsics, extrinsics))
+            rig_of_sample.append(index[key])
+        if len({t[0].shape[0] for t in tables}) != 1:
+            raise ValueError("every rig of a batch must have the same number of cameras")
+        if len(tables) == 1:
+            origin, direction = tables[0][0].unsqueeze(0), tables[0][1].unsqueeze(0)
+        else:
+            origin, direction = torch.stack([t[0] for t in tables]), torch.stack([t[1] for t in tables])
+        return O.ors_first_hit(occ, origin, direction, rig_of_sample, self.image_shape_compress, self.sample_point,
+                               self.sample_step, mode=mode, palette=OCC_COLORS if palette is None else palette,
+                               want_frames=want_frames, want_classes=want_classes, **kw)
+
+    def render_volume(self, occ, intrinsics, extrinsics, mode="bg", want_classes=False):
+        """The panorama of one volume and rig: (h, n_cam * w, 3) uint8, the colour of the first class along each ray that
+        is not 17 after the mode's filter ("all": none; "bg": classes <= 10 removed; "fg": classes >= 11 removed), the
+        views side by side; with want_classes also the classes, (n_cam, h, w) uint8, 17 where nothing was hit."""
+        frames, cls = self.render_batch([occ], [(intrinsics, extrinsics)], mode=mode, want_classes=want_classes)
+        return (frames[0], cls[0]) if want_classes else frames[0]
+
+    def render(self, sample_tokens, mode="bg"):
+        """The panoramas of a batch of tokens in one launch: (bs, h, n_cam * w, 3) uint8, what the reference reads from
+        ./occ_proj/occ_bg/{token}.png (misc/test_utils.py:219-222)."""
+        if self.occ_loader is None:
+            raise RuntimeError("OccupancyRay.render needs an occ_loader (token -> 200 x 200 x 16 class volume)")
+        tokens = list(sample_tokens)
+        return self.render_batch([self.occ_loader(t) for t in tokens], [self._rig(t) for t in tokens], mode=mode)[0]
 
     def _rig(self, sample_token):
         mats = [self.camera_matrices(self.camera_data[sample_token][c]) for c in CAMERAS]

@@ -1494,6 +1494,87 @@ def ors_project(occ, origin, direction, samples, step=0.2, *, want_labels=True, 
     return labels, cond
 
 
+ORS_MODES = {"all": 0, "bg": 1, "fg": 2}
+ORS_OVERLAY_FLAGS = ((1, "a sample's camera picture is constant (max == min): its blend is 0 / 0 in the reference"),)
+
+
+def ors_first_hit(occ, origin, direction, rig_of_sample, size, samples, step=0.2, *, mode="bg", palette,
+                  want_frames=True, want_classes=False, want_visited=False, exits=3):
+    """The ORS panorama in one launch (include/dualdiff_hip.h: dd_ors_first_hit; networks/occ3d_proj.py:156-198).
+    occ: (b, 200, 200, 16) uint8 on the GPU; origin (r, n, 3), direction (r, n, h * w, 3) fp32 on the GPU: the ray tables
+    of r rigs; rig_of_sample: b integers in [0, r) (host sequence or tensor; the range is checked here, on the host);
+    size = (h, w); palette: 18 (r, g, b) byte triples.  -> (frames (b, h, n * w, 3) uint8 | None, cls (b, n, h, w) uint8
+    | None), and the per-ray count of samples looked up, (b, n, h, w) int32, as a third item with want_visited."""
+    lib = _native.load()
+    _need_gpu(occ, origin, direction)
+    if occ.dtype != torch.uint8 or occ.dim() != 4 or tuple(occ.shape[1:]) != (200, 200, 16) or not occ.is_contiguous():
+        raise ValueError("occ must be a contiguous (b, 200, 200, 16) uint8 batch of volumes, got %s %s"
+                         % (occ.dtype, tuple(occ.shape)))
+    if origin.dtype != torch.float32 or direction.dtype != torch.float32:
+        raise TypeError("origin and direction must be fp32, got %s and %s" % (origin.dtype, direction.dtype))
+    try:
+        h, w = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError("size must be (h, w), got %r" % (size,))
+    if h <= 0 or w <= 0 or int(samples) <= 0 or not float(step) > 0:
+        raise ValueError("size, samples and step must be positive, got %r, %r, %r" % (size, samples, step))
+    if origin.dim() != 3 or origin.shape[2] != 3 or direction.dim() != 4 or \
+            tuple(direction.shape) != (origin.shape[0], origin.shape[1], h * w, 3):
+        raise ValueError("origin must be (r, n, 3) and direction (r, n, %d, 3), got %s and %s"
+                         % (h * w, tuple(origin.shape), tuple(direction.shape)))
+    if mode not in ORS_MODES:
+        raise ValueError("mode must be one of %s, got %r" % (", ".join(ORS_MODES), mode))
+    if exits not in (0, 1, 2, 3):
+        raise ValueError("exits must be 0 .. 3, got %r" % (exits,))
+    if not (want_frames or want_classes):
+        raise ValueError("ors_first_hit writes frames, classes or both: both were declined")
+    pal = [int(c) for row in palette for c in row]
+    if len(pal) != 54 or any(not 0 <= c <= 255 for c in pal):
+        raise ValueError("palette must be 18 (r, g, b) byte triples")
+    b, (r, n) = occ.shape[0], origin.shape[:2]
+    rig = torch.as_tensor(rig_of_sample).detach().cpu().reshape(-1)
+    if rig.dtype.is_floating_point or rig.dtype == torch.bool or rig.numel() != b:
+        raise ValueError("rig_of_sample must be %d integers, got %s %s" % (b, rig.dtype, tuple(rig.shape)))
+    if int(rig.min()) < 0 or int(rig.max()) >= r:
+        raise ValueError("rig_of_sample must lie in [0, %d), got %s" % (r, rig.tolist()))
+    rig = rig.to(torch.int32).to(occ.device)
+    origin, direction = origin.contiguous(), direction.contiguous()
+    frames = torch.empty((b, h, n * w, 3), dtype=torch.uint8, device=occ.device) if want_frames else None
+    cls = torch.empty((b, n, h, w), dtype=torch.uint8, device=occ.device) if want_classes else None
+    visited = torch.empty((b, n, h, w), dtype=torch.int32, device=occ.device) if want_visited else None
+    arr = (ctypes.c_uint8 * 54)(*pal)
+    _native.check(lib.dd_ors_first_hit(_ptr(occ), _ptr(origin), _ptr(direction), _ptr(rig), _ptr(cls), _ptr(frames),
+                                       _ptr(visited), ctypes.cast(arr, ctypes.c_void_p), b, r, n, h, w, int(samples),
+                                       float(step), ORS_MODES[mode], int(exits), _stream()), "ors_first_hit")
+    return (frames, cls, visited) if want_visited else (frames, cls)
+
+
+def ors_overlay(frames, camera):
+    """The blend of ORS panoramas over camera panoramas of the same shape in two launches (include/dualdiff_hip.h:
+    dd_ors_overlay_u8; networks/occ3d_proj.py:196-203).  frames, camera: (b, h, W, 3) uint8 on the GPU.  -> (out (b, h, W,
+    3) uint8, flags (1,) int32: an OR of ORS_OVERLAY_FLAGS' bits).  Nothing is read back."""
+    lib = _native.load()
+    for name, t in (("frames", frames), ("camera", camera)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("ors_overlay: %s must be a tensor, got %s" % (name, type(t).__name__))
+        if t.dtype != torch.uint8:
+            raise TypeError("ors_overlay: %s must be uint8, got %s" % (name, t.dtype))
+    _need_gpu(frames, camera)
+    if frames.dim() != 4 or frames.shape[-1] != 3 or frames.numel() == 0:
+        raise ValueError("ors_overlay: frames must be (b, h, W, 3), got %s" % (tuple(frames.shape),))
+    if camera.shape != frames.shape:
+        raise ValueError("ors_overlay: the camera panorama must have the frames' shape %s, got %s (resize it first)"
+                         % (tuple(frames.shape), tuple(camera.shape)))
+    frames, camera = frames.contiguous(), camera.contiguous()
+    b, h, w = frames.shape[:3]
+    out = torch.empty_like(frames)
+    parts = torch.empty((b, 64, 2), dtype=torch.int32, device=frames.device)
+    flags = torch.empty((1,), dtype=torch.int32, device=frames.device)
+    _native.check(lib.dd_ors_overlay_u8(_ptr(frames), _ptr(camera), _ptr(out), _ptr(parts), _ptr(flags), b, h, w,
+                                        _stream()), "ors_overlay")
+    return out, flags
+
+
 def fourier_embed(x, freqs, include_input=True):
     """[x, sin(f0 x), cos(f0 x), ...] on the last dim (networks/embedder.py), one kernel."""
     lib = _native.load()

@@ -1,8 +1,8 @@
-"""The pipeline's modules are imported by their dotted paths; `MapRender` (map_output.py) and `BoxOverlay`
-(box_output.py) are also names of the package, resolved on first use so that importing one module does not import the
-others."""
+"""The pipeline's modules are imported by their dotted paths; `MapRender` (map_output.py), `BoxOverlay`
+(box_output.py) and `OccRender` (occ_render.py) are also names of the package, resolved on first use so that importing one
+module does not import the others."""
 
-_LAZY = {"MapRender": "map_output", "BoxOverlay": "box_output"}
+_LAZY = {"MapRender": "map_output", "BoxOverlay": "box_output", "OccRender": "occ_render"}
 
 
 def __getattr__(name):

@@ -415,6 +415,34 @@ int dd_ors_project(const uint8_t* occ, const float* origin, const float* dir, ui
                    int32_t n_cam, int32_t hw, int32_t samples, float step, int32_t keep_fg, int32_t keep_bg,
                    int32_t dtype, dd_stream_t stream);
 
+/* ORS panorama, the image-mode condition (networks/occ3d_proj.py:156-198; read as ./occ_proj/occ_bg/{token}.png by
+ * misc/test_utils.py:219-222): the FIRST occupied class along each ray, painted with a palette, the views side by side.
+ * The samples and their labels are dd_ors_project's; nothing per sample is written.  One launch for a batch.
+ *   occ [b][200][200][16] uint8; origin [rigs][n][3], dir [rigs][n][h * w][3] fp32; rig_of_sample [b] int32 DEVICE memory,
+ *   each in [0, rigs): the ray table sample i uses (the caller checks the range; a value outside gives class 17);
+ *   mode: 0 all labels count; 1 (bg) labels <= 10 become 17 first (:157); 2 (fg) labels >= 11 become 17 first (:160);
+ *   the first sample s in 0 .. samples - 1 whose label is not 17 gives the class (:165-168), 17 when there is none.  Class
+ *   0 is a class: it hides what lies behind it in modes 0 and 2.
+ *   cls (may be NULL): uint8 [b][n][h][w], the class;
+ *   frames (may be NULL): uint8 [b][h][n * w][3], its colour, palette[class] (:192-197); not both NULL;
+ *   visited (may be NULL): int32 [b][n][h][w], the number of samples the ray looked up (for measurements);
+ *   palette: 18 x 3 bytes in HOST memory, passed on by value (colors_map[:, :3] of :171-191 is the reference's);
+ *   exits: bit 0 stop at the first hit, bit 1 stop once the ray has left the volume for good; 3 for use, the results are
+ *   the same for every value.  step > 0. */
+int dd_ors_first_hit(const uint8_t* occ, const float* origin, const float* dir, const int32_t* rig_of_sample,
+                     uint8_t* cls, uint8_t* frames, int32_t* visited, const uint8_t* palette, int32_t b, int32_t rigs,
+                     int32_t n, int32_t h, int32_t w, int32_t samples, float step, int32_t mode, int32_t exits,
+                     dd_stream_t stream);
+
+/* The blend of an ORS panorama over the camera pictures (networks/occ3d_proj.py:196-203), all uint8 [b][h][w][3], w the
+ * width of the whole panorama.  Per sample: x = u8 / 255 * 2 - 1 (:127-129), d = (x - min x) / (max x - min x) * 255
+ * (:196); per channel element with colour c: c * 0.7f + d * 0.3f where c != 0, d where c == 0 (:199-203), truncated to
+ * uint8; float32 operation by operation, as numpy and torch apply it on the CPU.  Two launches: the reduction and the
+ * blend.  parts: int32 [b][64][2] workspace; flags: one int32, written: bit 0 = a sample's camera picture is constant
+ * (max == min, NaN in the reference; that sample's output is 0). */
+int dd_ors_overlay_u8(const uint8_t* colour, const uint8_t* camera, uint8_t* out, int32_t* parts, int32_t* flags,
+                      int32_t b, int32_t h, int32_t w, dd_stream_t stream);
+
 /* Row softmax of fp32 logits into the storage type: p[r][c] = softmax_c(s[r][c]) for c < cols
  * (diffusers AttnProcessor `get_attention_scores` with upcast_softmax — the single 512-wide head of
  * the VAE decoder's mid-block attention, decode_latents pipeline_bev_controlnet.py:101-113).
