@@ -24,7 +24,9 @@ SOURCES = ["gemm23.hip", "gemm2_conv.hip", "attention.hip", "gemm1.hip", "conv3s
            # the step's kernels instead of moving them
            "conv2d.hip",
            # the ORS panorama render runs before the first step: behind everything, for the same reason
-           "ors_render.hip"]
+           "ors_render.hip",
+           # the map input runs in the data path, before the first step: behind everything, for the same reason
+           "bev_map.hip"]
 # per-source extra flags: the attention softmax lives on the MFMA results, so ask LLVM for the
 # VGPR-destination form of MFMA (gfx950 has a unified register file) instead of AGPR accumulators
 # that cost a v_accvgpr_read/write per touched element.

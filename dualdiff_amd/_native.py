@@ -10,7 +10,7 @@ import os
 # and the process must end up with ONE HIP runtime (ours resolves to the already-loaded soname);
 # loading ours first gives two runtimes and every launch on a torch stream fails.
 import torch  # noqa: F401
-from ctypes import (POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_uint32, c_void_p)
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_int64, c_uint32, c_void_p)
 
 from . import _build
 
@@ -150,6 +150,10 @@ SIGNATURES = {
                                    c_void_p]),
     "dd_ors_overlay_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                     c_void_p]),
+    "dd_bev_map_workspace_bytes": (c_int64, [c_int32]),
+    "dd_bev_map_layers": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_double, c_double, c_double,
+                                    c_double, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dd_fourier_embed": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, POINTER(c_float), c_int32, c_int32,
                                    c_int32, c_int32, c_void_p]),
     "dd_conv3x3_small_cout": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,

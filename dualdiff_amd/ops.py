@@ -954,6 +954,97 @@ def box_draw_u8(frames, pts, cls, counts, palette, transparent=False, size=None)
     return out
 
 
+BEV_MAP_MAX_LAYERS = 30                          # include/dualdiff_hip.h: DD_BEV_MAP_MAX_LAYERS, one_hot_encode's limit
+BEV_MAP_AUX = (("visibility", 1, 1), ("center_offset", 2, 2), ("center_ohw", 4, 4), ("height", 8, 1))   # name, bit, channels
+
+
+def bev_map_aux_channels(aux_sel):
+    return sum(ch for _, bit, ch in BEV_MAP_AUX if aux_sel & bit)
+
+
+def bev_map_workspace_bytes(total):
+    n = _native.load().dd_bev_map_workspace_bytes(int(total))
+    if n < 0:
+        raise _native.Unsupported("dualdiff_amd.bev_map_layers: %d boxes are more than one call takes" % total)
+    return n
+
+
+def bev_map_layers(static, corners, bottom_center, height, visibility, labels, offsets, size, ns, nd, aux_sel, l2c, *,
+                   workspace=None, out=None):
+    """The BEV object layers and aux channels of a batch in two launches (include/dualdiff_hip.h: dd_bev_map_layers;
+    dataset/pipeline.py:88-217).  static: uint8 (b, ns, S, S) holding 0 / 1, or int32 (b, S, S) bit fields, or None with ns
+    = 0; corners (total, 8, 3), bottom_center (total, 3), height, visibility (total,) fp32, labels (total,) int64, offsets
+    (b + 1,) int32 — contiguous device tensors; size = S; aux_sel: an OR of BEV_MAP_AUX's bits; l2c = (sx, ox, sy, oy):
+    canvas x = x * sx + ox.  workspace: a uint8 device tensor of at least bev_map_workspace_bytes(total) bytes, 16-byte
+    aligned (default: a new one); out = (masks, aux, flags) to write into (default: new ones).
+    -> (masks (b, ns + nd, S, S) uint8, aux (b, ch, S, S) fp32 or None, flags (1,) int32: the number of boxes whose quad
+    is of the family that is not drawn).  Nothing is read back."""
+    what = "bev_map_layers"
+    size, ns, nd, aux_sel = int(size), int(ns), int(nd), int(aux_sel)
+    if size <= 0 or ns < 0 or nd < 0 or ns + nd == 0:
+        raise ValueError("%s: size must be positive and ns + nd > 0, got %d, %d + %d" % (what, size, ns, nd))
+    if ns + nd > BEV_MAP_MAX_LAYERS:
+        raise ValueError("%s: at most %d layers, got %d + %d" % (what, BEV_MAP_MAX_LAYERS, ns, nd))
+    if not 0 <= aux_sel <= 15:
+        raise ValueError("%s: aux_sel must be an OR of the bits 1, 2, 4, 8, got %d" % (what, aux_sel))
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.shape[0] < 2:
+        raise ValueError("%s takes int32 offsets (b + 1,), got %s %s" % (what, offsets.dtype, tuple(offsets.shape)))
+    b = offsets.shape[0] - 1
+    if corners.dim() != 3 or tuple(corners.shape[1:]) != (8, 3) or corners.dtype != torch.float32:
+        raise ValueError("%s takes fp32 corners (total, 8, 3), got %s %s" % (what, corners.dtype, tuple(corners.shape)))
+    total = corners.shape[0]
+    for name, t, shape, dt in (("bottom_center", bottom_center, (total, 3), torch.float32),
+                               ("height", height, (total,), torch.float32),
+                               ("visibility", visibility, (total,), torch.float32), ("labels", labels, (total,), torch.int64)):
+        if t.dtype != dt or tuple(t.shape) != shape:
+            raise ValueError("%s takes %s %s %s, got %s %s" % (what, dt, name, shape, t.dtype, tuple(t.shape)))
+    bits = False
+    if ns > 0:
+        if static is None:
+            raise ValueError("%s: %d static layers and no static input" % (what, ns))
+        if static.dtype == torch.int32 and tuple(static.shape) == (b, size, size):
+            bits = True
+        elif static.dtype != torch.uint8 or tuple(static.shape) != (b, ns, size, size):
+            raise ValueError("%s takes static layers uint8 (%d, %d, %d, %d) or bit fields int32 (%d, %d, %d), got %s %s"
+                             % (what, b, ns, size, size, b, size, size, static.dtype, tuple(static.shape)))
+    else:
+        static = None
+    try:
+        sx, ox, sy, oy = (float(v) for v in l2c)
+    except (TypeError, ValueError):
+        raise ValueError("%s: l2c must be (sx, ox, sy, oy), got %r" % (what, l2c))
+    ins = (static, corners, bottom_center, height, visibility, labels, offsets)
+    if any(t is not None and not t.is_contiguous() for t in ins):
+        raise ValueError("%s takes contiguous tensors" % what)
+    _need_gpu(*ins)
+    dev = offsets.device
+    need = bev_map_workspace_bytes(total)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
+        raise ValueError("%s: the workspace must be a contiguous uint8 tensor of at least %d bytes" % (what, need))
+    ch = bev_map_aux_channels(aux_sel)
+    if out is None:
+        masks = torch.empty((b, ns + nd, size, size), dtype=torch.uint8, device=dev)
+        aux = torch.empty((b, ch, size, size), dtype=torch.float32, device=dev) if ch else None
+        flags = torch.empty((1,), dtype=torch.int32, device=dev)
+    else:
+        masks, aux, flags = out
+        if masks.dtype != torch.uint8 or tuple(masks.shape) != (b, ns + nd, size, size) or not masks.is_contiguous() \
+                or flags.dtype != torch.int32 or flags.numel() != 1 or (aux is None) != (ch == 0) \
+                or (aux is not None and (aux.dtype != torch.float32 or tuple(aux.shape) != (b, ch, size, size)
+                                         or not aux.is_contiguous())):
+            raise ValueError("%s: out must be (uint8 (%d, %d, %d, %d), fp32 (%d, %d, %d, %d) or None, int32 (1,))"
+                             % (what, b, ns + nd, size, size, b, ch, size, size))
+    _need_gpu(workspace, masks, aux, flags)
+    lib = _native.load()
+    _native.check(lib.dd_bev_map_layers(_ptr(static), 1 if bits else 0, _ptr(corners), _ptr(bottom_center), _ptr(height),
+                                        _ptr(visibility), _ptr(labels), _ptr(offsets), total, b, size, ns, nd, aux_sel,
+                                        sx, ox, sy, oy, _ptr(workspace), workspace.numel(), _ptr(masks), _ptr(aux),
+                                        _ptr(flags), _stream()), what)
+    return masks, aux, flags
+
+
 MAP_MAX_LAYERS = 31                              # include/dualdiff_hip.h: DD_MAP_MAX_LAYERS; bit 31 of `used` is taken
 MAP_SIDES = {"right": 0, "below": 1}
 

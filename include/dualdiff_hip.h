@@ -910,6 +910,48 @@ int dd_box_draw_u8(const uint8_t* frames, const int32_t* pts, const int32_t* cls
                    int32_t transparent, dd_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Map input (csrc/bev_map.hip, csrc/bev_map_core.h): the BEV object layers and aux channels that the reference's
+ * LoadBEVSegmentationM makes from the 3D boxes on the host (magicdrive/dataset/pipeline.py: _project_dynamic_bbox
+ * :176-200 and the transpose of :215; _get_dynamic_aux_bbox :88-152 and the transpose of :173), joined to the static
+ * layers, which may arrive as the int32 bit fields of the h5 cache (one_hot_decode, dataset/pipeline_utils.py:34-49).
+ * Two launches: dd_bev_box_records (one lane per box: its 208-byte record into the workspace) and dd_bev_map_layers
+ * (pixel-major, a workgroup per 16 x 16 tile and sample).  No atomics, nothing cleared, nothing allocated.
+ *   stat: static_bits = 0: uint8 [b][ns][size][size] holding 0 / 1, copied; static_bits = 1: int32 [b][size][size], layer
+ *     c = bit c (4-byte aligned).  May be NULL with ns = 0.
+ *   corners fp32 [total][8][3] (the caller's box.corners), bottom_center fp32 [total][3], height, visibility fp32 [total],
+ *   labels int64 [total]; offsets int32 [b + 1]: sample i owns boxes offsets[i] .. offsets[i + 1] - 1 in input order
+ *   (values are clamped to [0, total]).  All device memory.
+ *   sx, ox, sy, oy: lidar2canvas (:70-74): canvas x = x * sx + ox and canvas y = y * sy + oy in float64, two roundings;
+ *     the vertex is np.round (half to even) of that, cast to int32, saturated at +-2^20.  Ring: corners 0, 3, 7, 4.
+ *   masks: uint8 [b][ns + nd][size][size], any alignment: the static layers, then layer ns + c = the union of PIL's
+ *     ImageDraw.polygon(fill=1) of the boxes with label c, at [x][y] (the transposed picture); labels outside [0, nd)
+ *     draw no layer.
+ *   aux (NULL iff aux_sel = 0): fp32 [b][ch][size][size] at [x][y], the channels of the LAST box in input order whose
+ *     polygon covers the pixel, whatever its label, 0 where there is none; aux_sel: bit 0 visibility (1 channel), bit 1
+ *     center_offset (2: float32(x) - centre in float64), bit 2 center_ohw (4: |front - centre|, |left - centre|, (front -
+ *     centre) / (|front - centre| + 1e-6), float64 with IEEE division and square root, front / left the float32 means of
+ *     corners 4, 7 and 0, 4), bit 3 height (1), in this order.
+ *   flags: one int32, WRITTEN: the number of boxes whose rounded quad is of the family that is not drawn — two opposite
+ *     vertices equal, the other two distinct from them and from each other, one of them more than one pixel (Chebyshev)
+ *     from the repeated vertex; no rectangle rounds to such a quad.  Such a box draws nothing in masks and aux.
+ *   workspace: at least dd_bev_map_workspace_bytes(total) bytes, 16-byte aligned, contents don't care before and after.
+ * DD_ERR_BAD_ARG, before any runtime call: a NULL offsets / workspace / masks / flags, NULL stat with ns > 0, a NULL box
+ * array with total > 0, aux NULL with aux_sel != 0 or the reverse, static_bits not 0 / 1, total < 0, non-positive b /
+ * size / ns + nd, negative ns / nd, ns + nd > DD_BEV_MAP_MAX_LAYERS (one_hot_encode's limit), aux_sel outside [0, 15], a
+ * scale or offset that is not finite, a misaligned array, workspace_bytes too small.  total > DD_BEV_MAP_MAX_BOXES,
+ * size > DD_BEV_MAP_MAX_SIZE or b > 65535: DD_ERR_UNSUPPORTED; dd_bev_map_workspace_bytes returns -1 for such a total.
+ * ------------------------------------------------------------------------- */
+#define DD_BEV_MAP_MAX_LAYERS 30
+#define DD_BEV_MAP_MAX_BOXES (1 << 20)
+#define DD_BEV_MAP_MAX_SIZE 4096
+int64_t dd_bev_map_workspace_bytes(int32_t total);
+int dd_bev_map_layers(const void* stat, int32_t static_bits, const float* corners, const float* bottom_center,
+                      const float* height, const float* visibility, const int64_t* labels, const int32_t* offsets,
+                      int32_t total, int32_t b, int32_t size, int32_t ns, int32_t nd, int32_t aux_sel, double sx,
+                      double ox, double sy, double oy, void* workspace, int64_t workspace_bytes, uint8_t* masks,
+                      float* aux, int32_t* flags, dd_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * CLIP text encoder (csrc/clip.hip): the SD-v1.5 `text_encoder` (transformers.CLIPTextModel) that the reference calls at
  * runner/base_runner.py:119,511-514, runner/multiview_runner.py:145,427-428 (`text_encoder(ids)[0]`), through diffusers'
  * _encode_prompt at pipeline/pipeline_bev_controlnet.py:273 and at networks/bbox_embedder.py:133-145
