@@ -26,7 +26,9 @@ SOURCES = ["gemm23.hip", "gemm2_conv.hip", "attention.hip", "gemm1.hip", "conv3s
            # the ORS panorama render runs before the first step: behind everything, for the same reason
            "ors_render.hip",
            # the map input runs in the data path, before the first step: behind everything, for the same reason
-           "bev_map.hip"]
+           "bev_map.hip",
+           # the attention-map probe is launched only while a capture is installed: behind everything, for the same reason
+           "attn_probs.hip"]
 # per-source extra flags: the attention softmax lives on the MFMA results, so ask LLVM for the
 # VGPR-destination form of MFMA (gfx950 has a unified register file) instead of AGPR accumulators
 # that cost a v_accvgpr_read/write per touched element.
@@ -37,6 +39,7 @@ EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-hon
                **{src: ["-mllvm", "-amdgpu-mfma-vgpr-form=1"] for src in GEMM_SOURCES},
                # the causal softmax reads its whole score strip out of the MFMA results, as attention.hip's does
                "clip.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               "attn_probs.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                # the BatchNorm + ReLU epilogue reads every accumulator: VGPR results, as for the GEMM kernels
                "conv2d.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 ARCH = "gfx950"

@@ -641,12 +641,18 @@ class Attention(_Cached):
         if kv is None:
             kv = self.project_kv(ctx2d)
         lk_dev = lk_dev_for(ctx2d, lk)               # the context is laid out at a capacity: its real length (round 6)
+        probe = self.__dict__.get("_attn_probe")     # attn_maps.CrossAttnMapCapture: observes q and k, reroutes nothing
         if XATTN_FUSED and O.xattn320_ok(c, self.heads, lk, x2d.shape[0]) and self.to_q.in_features == c and self.to_q.bias is None \
                 and not ln_stats and LN_FOLD == "0":
             # 28x50 level: q-projection, attention over the <= 128 context keys and out-projection + residual in ONE
             # launch (csrc/xattn.hip); it owns whole rows, so it also emits the next sub-layer's LayerNorm
             xn = x2d if norm is None else norm.run(x2d)
             lno = (ln_next.weight, ln_next.bias, ln_next.eps) if LN_PRODUCER and isinstance(ln_next, LayerNorm) else None
+            if probe is not None:
+                # q never reaches memory on this path: the probe gets it from the to_q call the unfused path makes (one
+                # extra GEMM, for the probe only); the fused launch below still produces what flows on
+                probe(self, self.to_q.run(xn, **({"head_major": self._hm(self.heads)} if HEAD_MAJOR else {})), kv[:, :c],
+                      batch, lq, lk, HEAD_MAJOR, lk_dev)
             out = O.xattn320(xn, self.to_q.wx, self.to_out[0].wx, self.to_out[0].bias, kv[:, :c], kv[:, c:], batch, lq,
                              lk, self.scale, res=res, ln_out=lno, lk_dev=lk_dev)
             if lno is not None:
@@ -655,6 +661,8 @@ class Attention(_Cached):
         q_hm = HEAD_MAJOR and self.to_q.bias is None
         kw = {"head_major": self._hm(self.heads)} if q_hm else {}
         q = self.to_q.run(x2d, **kw) if norm is None else self.to_q.run_ln(x2d, norm, **kw)
+        if probe is not None:
+            probe(self, q, kv[:, :c], batch, lq, lk, q_hm, lk_dev)
         o = O.attention(q, kv[:, :c], kv[:, c:], batch, lq, lk, self.heads, self.dim_head, self.scale,
                         q_prescaled=q_hm, lk_dev=lk_dev)
         return self.to_out[0].run(o, res=res, ln_stats=ln_stats, ln_next=ln_next)

@@ -1243,6 +1243,63 @@ def attention(q, k, v, batch, lq, lk, heads, head_dim, scale=None, *, kv_batch_m
     return out
 
 
+ATTN_PROBS_MAX_LK = 256         # DD_ATTN_PROBS_MAX_LK of include/dualdiff_hip.h
+
+
+def attention_probs(q, k, batch, lq, lk, heads, head_dim, scale=None, *, q_prescaled=False, per_head=False, out=None,
+                    accumulate=False, weight=1.0, lk_dev=None):
+    """softmax(scale * q k^T) itself, in float32 (dd_attn_probs) — the probabilities `attention` and `xattn320` never
+    write: (batch, heads, lq, lk) with per_head, else their mean over the heads (batch, lq, lk), times `weight`.
+
+    q / k as `attention` takes them: (batch*l, >= heads*head_dim) row-strided 2-D views (column slices of a fused
+    projection) or head-major 3-D tensors (heads, rows, head_dim); q_prescaled: q carries scale * log2(e).  Row slices
+    of either form select batch entries without a copy.  out: float32 (batch, [heads,] lq, lk) with unit inner stride
+    (a row pitch that is a multiple of 4 floats on a 16-byte aligned base takes the vector stores); accumulate: add to
+    `out` instead of storing.  lk_dev as in `attention`: the real key count, `lk` the capacity; a store then writes the
+    columns past it as zeros, an accumulate leaves them alone.  head_dim 40 / 80 / 160, lk <= ATTN_PROBS_MAX_LK."""
+    batch, lq, lk, heads, head_dim = int(batch), int(lq), int(lk), int(heads), int(head_dim)
+    if min(batch, lq, lk, heads, head_dim) <= 0:
+        raise ValueError("attention_probs: batch, lq, lk, heads and head_dim must be positive")
+    if q.dtype != k.dtype:
+        raise ValueError("attention_probs: q is %s, k is %s" % (q.dtype, k.dtype))
+
+    def operand(t, l, name):
+        if t.dim() == 3:
+            if t.shape[0] != heads or t.shape[1] != batch * l or t.shape[2] != head_dim or t.stride(2) != 1 \
+                    or t.stride(1) != head_dim:
+                raise ValueError("attention_probs: head-major %s must be (%d, %d, %d) with contiguous rows, got %s"
+                                 % (name, heads, batch * l, head_dim, tuple(t.shape)))
+            return t.data_ptr(), head_dim, l * head_dim, t.stride(0)
+        if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != batch * l or t.shape[1] < heads * head_dim:
+            raise ValueError("attention_probs: %s must be a (%d, >= %d) view with unit inner stride, got shape %s stride %s"
+                             % (name, batch * l, heads * head_dim, tuple(t.shape), t.stride()))
+        return t.data_ptr(), t.stride(0), l * t.stride(0), 0
+    qa, ka = operand(q, lq, "q"), operand(k, lk, "k")
+    shape = (batch, heads, lq, lk) if per_head else (batch, lq, lk)
+    if out is None:
+        if accumulate:
+            raise ValueError("attention_probs: accumulate needs out")
+    elif tuple(out.shape) != shape or out.stride(-1) != 1:
+        raise ValueError("attention_probs: out must be %s with unit inner stride, got shape %s stride %s"
+                         % (shape, tuple(out.shape), out.stride()))
+    _dtype_code(q.dtype)
+    _check_lk_dev(lk_dev)
+    _need_gpu(q, k, out, lk_dev)
+    lib = _native.load()
+    if out is None:             # rows at a pitch of whole float4 groups
+        out = torch.empty(shape[:-1] + ((lk + 3) // 4 * 4,), dtype=torch.float32, device=q.device)[..., :lk]
+    elif out.dtype != torch.float32:
+        raise TypeError("attention_probs: out must be torch.float32")
+    _timer.launch("attention_probs", lib.dd_attn_probs, _ptr(q), _ptr(k), _ptr(out), qa[1], ka[1], qa[2], ka[2], qa[3],
+                  ka[3], out.stride(-2), out.stride(0), out.stride(1) if per_head else 0, batch, lq, lk, heads, head_dim,
+                  float(scale) if scale is not None else head_dim ** -0.5, int(bool(q_prescaled)), int(bool(per_head)),
+                  int(bool(accumulate)), float(weight), _ptr(lk_dev), _dt(q), _stream(),
+                  book=lambda: ("dd_attn_probs_kernel<%s,D%d>" % (_tname(_dt(q)), head_dim),
+                                2.0 * batch * heads * lq * lk * head_dim,
+                                2.0 * heads * head_dim * batch * (lq + lk) + 4.0 * out.numel() * (2 if accumulate else 1)))
+    return out
+
+
 def causal_attention(q, k, v, batch, l, heads, head_dim, out=None):
     """softmax_{j <= i}(head_dim^-0.5 * q_i . k_j) v_j per (sequence, head) — CLIP's self-attention (dd_causal_attention:
     head_dim 64, l <= CAUSAL_ATTN_MAX_L).  q, k, v: (batch*l, >= heads*head_dim) row-strided views, so the column slices

@@ -97,7 +97,8 @@ class BEVDenoiser:
     def __init__(self, unet, controlnets: List, guidance_scale=2.0, num_inference_steps=50,
                  conditioning_scale=1.0, hoist_invariant=False, use_graph=True, use_aug_text=False,
                  parallel_branches=True, cfg_half: Optional[int] = None, cfg_exchange=None,
-                 sampler="ddim", view_shard=None, frame_shard=None, segmented_graph=True):
+                 sampler="ddim", view_shard=None, frame_shard=None, segmented_graph=True, attn_maps=None,
+                 attn_maps_reduce=None):
         self.unet = unet
         self.controlnets = list(controlnets)
         self.guidance_scale = float(guidance_scale)
@@ -117,8 +118,19 @@ class BEVDenoiser:
             self.timesteps, self.coef_table = unipc_schedule(num_inference_steps)
             self.num_inference_steps = len(self.timesteps)
         self._graph = None
+        self._graph_epoch = None            # layers.CACHE_EPOCH the step graph was recorded in (looked at with attn_maps only)
+        self._graph_keep = None             # attention-map buffers the recorded probe launches write to
         self._prepared = None
         self._segmented = False
+        # Cross-attention maps (networks/attn_maps.CrossAttnMapCapture over the UNet and the ControlNets): run() leaves
+        # the reference's `cross_attn_map` in self.cross_attn_map (explore_pipeline_bev_controlnet.py:352-354,437-453,
+        # 494-500,576).  attn_maps_reduce: None keeps the maps of every step, "mean" only their mean over the steps.
+        if attn_maps_reduce not in (None, "mean"):
+            raise ValueError("attn_maps_reduce is None or 'mean'")
+        if attn_maps is None and attn_maps_reduce is not None:
+            raise ValueError("attn_maps_reduce needs attn_maps")
+        self.attn_maps, self.attn_maps_reduce = attn_maps, attn_maps_reduce
+        self.cross_attn_map = None
         self._given = None                  # ops.GivenViews of the current inputs (set_inputs' conditional_latents)
         # view split + use_graph: record the step as graph SEGMENTS with the exchanges between them (default) instead of
         # one graph that would have to contain the point-to-point operations
@@ -378,6 +390,23 @@ class BEVDenoiser:
         torch.cuda.current_stream().wait_stream(s)
         restore()
         self._graph = g
+        from ..networks import layers as _layers
+        self._graph_epoch = _layers.CACHE_EPOCH[0]
+        # probe launches in the graph write to buffers their capture owns: they live as long as the graph does
+        self._graph_keep = [dict(p.buffers) for net in [self.unet] + self.controlnets for mod in net.modules()
+                            for p in [mod.__dict__.get("_attn_probe")] if p is not None] or None
+
+    def _record_if_needed(self):
+        """Records the step graph when there is none — or, with attn_maps, when it was recorded with another set of probe
+        launches (a capture installed, removed or switched between storing and accumulating since).  True if it did."""
+        if self._graph is not None and self.attn_maps is not None:
+            from ..networks import layers as _layers
+            if self._graph_epoch != _layers.CACHE_EPOCH[0]:
+                self._graph = None
+        if self._graph is not None:
+            return False
+        self.capture()
+        return True
 
     def step(self, i):
         """Denoising step i (0-based) on the current latents."""
@@ -385,8 +414,7 @@ class BEVDenoiser:
         sibling_barrier()                                # this step rewrites its buffers in place (no version counts)
         self._set_step(i)
         if self.use_graph:
-            if self._graph is None:
-                self.capture()
+            if self._record_if_needed():
                 self._set_step(i)
             self._graph.replay()
         else:
@@ -395,8 +423,45 @@ class BEVDenoiser:
             self._combine_halves()
 
     def run(self, steps: Optional[int] = None):
-        for i in range(steps if steps is not None else self.num_inference_steps):
+        steps = steps if steps is not None else self.num_inference_steps
+        if self.attn_maps is not None:
+            return self._run_with_maps(steps)
+        for i in range(steps):
             self.step(i)
+        return self.latents
+
+    # ------------------------------------------------------------------- attention maps ----
+    def _map_sources(self):
+        """(slot, name prefix, model) of every observed model that this denoiser runs: the ControlNet container's names
+        (diffusers' MultiControlNetModel: `nets.<i>.` when there are several) and the UNet's."""
+        cap, multi = self.attn_maps, len(self.controlnets) > 1
+        src = [("cnet", "nets.%d." % i if multi else "", cn) for i, cn in enumerate(self.controlnets)]
+        src.append(("unet", "", self.unet))
+        return [(slot, prefix, net) for slot, prefix, net in src if any(net is m for m in cap.models)]
+
+    def _run_with_maps(self, steps):
+        cap, mean = self.attn_maps, self.attn_maps_reduce == "mean"
+        cap.install()
+        cap.accumulate(1.0 / steps if mean else None)
+        if mean:
+            if self.use_graph:                       # the warm-ups of the capture add to the buffers: record first
+                self._set_step(0)
+                self._record_if_needed()
+            cap.zero_()
+        cnet, unet = {}, {}
+        slots = {"cnet": cnet, "unet": unet}
+        for i in range(steps):
+            self.step(i)
+            if not mean:                             # device-to-device copies, after the replay of the step graph
+                t = int(self.timesteps[i])
+                for slot, prefix, net in self._map_sources():
+                    slots[slot].setdefault(t, {}).update({prefix + k: v for k, v in cap.collect(net).items()})
+        if mean:
+            for slot, prefix, net in self._map_sources():
+                slots[slot].setdefault("mean", {}).update({prefix + k: v for k, v in cap.collect(net).items()})
+        # 'cnet'[1] is the reference's cross_attn_viz_c_adapter: the adapter's own attentions, not captured (and empty
+        # in the reference's saved files, tools/explore_attn.py:62)
+        self.cross_attn_map = {"cnet": [cnet, {}], "unet": unet}
         return self.latents
 
     @property

@@ -284,6 +284,36 @@ int dd_attention(const dd_attn_desc* d, dd_stream_t stream);
 const char* dd_attention_kernel_name(const dd_attn_desc* d);
 
 /* ------------------------------------------------------------------------- *
+ * Cross-attention probabilities (csrc/attn_probs.hip): the numbers dd_attention and dd_xattn320 never write.
+ *   w[b,h,i,j] = softmax_{j < n}( scale * Q[b,i,h,:] . K[b,j,h,:] )       n = lk_dev ? clamp(lk_dev[0], 1, lk) : lk
+ *   per_head = 1:  P[b,h,i,j] (op)= weight * w[b,h,i,j]
+ *   per_head = 0:  P[b,i,j]   (op)= weight * (1 / heads) * sum_h w[b,h,i,j]     (fp32 sum in ascending h)
+ * Replaces the probabilities the reference's visualisation processor keeps, tools/unet_modify.py:31,47
+ * (attn.get_attention_scores of every attn2 layer), which pipeline/explore_pipeline_bev_controlnet.py:352-354,437-453,
+ * 494-500,576 collects as cross_attn_map and tools/explore_attn.py:97-151 averages over heads, steps and layers.
+ * Q / K are addressed as in dd_attn_desc (ldq / ldk, batch strides, head strides with 0 = head_dim; q_prescaled = 1: q
+ * carries scale * log2 e and `scale` is ignored), elements of `qk_dtype` (DD_F16 / DD_BF16).  P is FLOAT32: element
+ * (b, [h,] i, j) at  b * p_batch_stride [+ h * p_head_stride] + i * ldp + j  (elements; p_head_stride is ignored for
+ * per_head = 0).  accumulate = 0 stores, and columns n .. lk-1 are then written as exact zeros; accumulate = 1 adds to
+ * what is there and does not touch columns n .. lk-1.  Nothing is written outside columns 0 .. lk-1 of a row.
+ * Arithmetic: fp32 MFMA scores of the 16-bit operands; the EXACT row maximum m over the n keys (a row of at most
+ * DD_ATTN_PROBS_MAX_LK scores stays in registers: no online rescale); p = exp2(fma(s, c, -m c)), c = scale * log2 e;
+ * the fp32 sum of the unrounded p; one normalisation; nothing is rounded to the storage type.  One wave owns a
+ * (batch entry, 16 query rows) across all heads: no atomics, identical bits from run to run, and a launch with lk_dev
+ * gives the bits of a launch with lk = lk_dev[0] and the same strides.
+ * head_dim in {40, 80, 160} and lk <= DD_ATTN_PROBS_MAX_LK, else DD_ERR_UNSUPPORTED.  DD_ERR_BAD_ARG: a NULL q / k / p,
+ * q / k not 16-byte aligned, p or lk_dev not 4-byte aligned, a non-positive batch / lq / lk / heads / head_dim, ld or
+ * strides of q / k that are negative or no multiples of 8, ldp < lk, a negative stride of p, scale <= 0 without
+ * q_prescaled, an unknown qk_dtype.  Both are decided before anything is launched.  (P rows go out as 16-byte stores
+ * where p is 16-byte aligned and ldp and its strides are multiples of 4, as single floats otherwise.) */
+#define DD_ATTN_PROBS_MAX_LK 256
+int dd_attn_probs(const void* q, const void* k, float* p, int64_t ldq, int64_t ldk, int64_t q_batch_stride,
+                  int64_t k_batch_stride, int64_t q_head_stride, int64_t k_head_stride, int64_t ldp,
+                  int64_t p_batch_stride, int64_t p_head_stride, int32_t batch, int32_t lq, int32_t lk, int32_t heads,
+                  int32_t head_dim, float scale, int32_t q_prescaled, int32_t per_head, int32_t accumulate,
+                  float weight, const int32_t* lk_dev, int32_t qk_dtype, dd_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Fused cross-attention of the 320-channel level (8 heads x 40, <= 128 context keys per view-instance), ONE launch:
  *   out[r, :] = ( softmax_j( scale * (x[r] Wq^T)_h . K[i, j]_h ) V[i, j]_h )_h Wo^T + bo + res[r, :]
  * for query row r of view-instance i = r / rows_per_inst; optionally also ln_out = LayerNorm(out) (two-pass fp32
