@@ -28,7 +28,10 @@ SOURCES = ["gemm23.hip", "gemm2_conv.hip", "attention.hip", "gemm1.hip", "conv3s
            # the map input runs in the data path, before the first step: behind everything, for the same reason
            "bev_map.hip",
            # the attention-map probe is launched only while a capture is installed: behind everything, for the same reason
-           "attn_probs.hip"]
+           "attn_probs.hip",
+           # the heat-map sheets are made of the captured maps after the last step: behind everything, for the same reason.
+           # No flag of its own below: its fp64 subtraction and division must stay IEEE-rounded (no fast-math, NaNs honoured)
+           "attn_heat.hip"]
 # per-source extra flags: the attention softmax lives on the MFMA results, so ask LLVM for the
 # VGPR-destination form of MFMA (gfx950 has a unified register file) instead of AGPR accumulators
 # that cost a v_accvgpr_read/write per touched element.

@@ -205,6 +205,10 @@ SIGNATURES = {
     "dd_attn_probs": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
                                 c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_int32,
                                 c_int32, c_float, c_void_p, c_int32, c_void_p]),
+    "dd_attn_heat": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64,
+                               c_int64, c_void_p]),
+    "dd_attn_sheet_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                   c_int32, c_int32, c_int32, c_void_p]),
     "dd_conv3x3_thin": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                   c_int32, c_int32, c_int32, c_void_p]),
     "dd_cfg_ddim_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,

@@ -256,6 +256,87 @@ def device_bilinear_tables(in_size, out_size, device):
     return device_const(("bilinear", n, out), device, lambda: bilinear_tables(n, out))
 
 
+# ---- the colour map of the attention heat maps (csrc/attn_heat.hip, pipeline/attn_output.py) ---------------------------
+
+# matplotlib's "coolwarm" as bytes: (cmap(arange(256))[:, :3] * 255).astype(uint8) of matplotlib 3.10, computed once and
+# kept as data so that nothing needs matplotlib at run time (tests/test_attn_output_cpu.py compares it where matplotlib
+# is installed)
+COOLWARM_U8 = (
+    (58, 76, 192), (59, 77, 193), (60, 79, 195), (62, 81, 196), (63, 83, 198), (64, 84, 199), (65, 86, 201), (66, 88, 202),
+    (67, 90, 204), (69, 91, 205), (70, 93, 207), (71, 95, 208), (72, 96, 209), (73, 98, 211), (75, 100, 212), (76, 102, 214),
+    (77, 103, 215), (78, 105, 216), (80, 107, 218), (81, 108, 219), (82, 110, 220), (83, 112, 221), (85, 113, 222), (86, 115, 224),
+    (87, 117, 225), (88, 118, 226), (90, 120, 227), (91, 121, 228), (92, 123, 229), (93, 125, 230), (95, 126, 231), (96, 128, 232),
+    (97, 130, 234), (99, 131, 234), (100, 133, 235), (101, 134, 236), (103, 136, 237), (104, 137, 238), (105, 139, 239), (107, 141, 240),
+    (108, 142, 241), (109, 144, 241), (111, 145, 242), (112, 147, 243), (113, 148, 244), (115, 149, 244), (116, 151, 245), (117, 152, 246),
+    (119, 154, 246), (120, 155, 247), (122, 157, 248), (123, 158, 248), (124, 160, 249), (126, 161, 249), (127, 162, 250), (128, 164, 250),
+    (130, 165, 251), (131, 166, 251), (133, 168, 251), (134, 169, 252), (135, 170, 252), (137, 172, 252), (138, 173, 253), (139, 174, 253),
+    (141, 175, 253), (142, 177, 253), (144, 178, 254), (145, 179, 254), (146, 180, 254), (148, 181, 254), (149, 183, 254), (151, 184, 254),
+    (152, 185, 254), (153, 186, 254), (155, 187, 254), (156, 188, 254), (157, 189, 254), (159, 190, 254), (160, 191, 254), (162, 192, 254),
+    (163, 193, 254), (164, 194, 254), (166, 195, 253), (167, 196, 253), (168, 197, 253), (170, 198, 253), (171, 199, 252), (172, 200, 252),
+    (174, 201, 252), (175, 202, 251), (176, 203, 251), (178, 203, 251), (179, 204, 250), (180, 205, 250), (182, 206, 249), (183, 207, 249),
+    (184, 207, 248), (185, 208, 248), (187, 209, 247), (188, 209, 246), (189, 210, 246), (190, 211, 245), (192, 211, 245), (193, 212, 244),
+    (194, 212, 243), (195, 213, 242), (197, 213, 242), (198, 214, 241), (199, 214, 240), (200, 215, 239), (201, 215, 238), (202, 216, 238),
+    (204, 216, 237), (205, 217, 236), (206, 217, 235), (207, 217, 234), (208, 218, 233), (209, 218, 232), (210, 218, 231), (211, 219, 230),
+    (213, 219, 229), (214, 219, 228), (215, 219, 226), (216, 219, 225), (217, 220, 224), (218, 220, 223), (219, 220, 222), (220, 220, 221),
+    (221, 220, 219), (222, 219, 218), (223, 219, 217), (224, 218, 215), (225, 218, 214), (226, 217, 212), (227, 217, 211), (228, 216, 209),
+    (229, 216, 208), (230, 215, 207), (231, 214, 205), (231, 214, 204), (232, 213, 202), (233, 212, 201), (234, 211, 199), (235, 211, 198),
+    (236, 210, 196), (236, 209, 195), (237, 208, 193), (237, 207, 192), (238, 207, 190), (239, 206, 188), (239, 205, 187), (240, 204, 185),
+    (241, 203, 184), (241, 202, 182), (242, 201, 181), (242, 200, 179), (242, 199, 178), (243, 198, 176), (243, 197, 175), (244, 196, 173),
+    (244, 195, 171), (244, 194, 170), (245, 193, 168), (245, 192, 167), (245, 191, 165), (246, 189, 164), (246, 188, 162), (246, 187, 160),
+    (246, 186, 159), (246, 185, 157), (246, 183, 156), (246, 182, 154), (247, 181, 152), (247, 179, 151), (247, 178, 149), (247, 177, 148),
+    (247, 176, 146), (247, 174, 145), (247, 173, 143), (246, 171, 141), (246, 170, 140), (246, 169, 138), (246, 167, 137), (246, 166, 135),
+    (246, 164, 134), (246, 163, 132), (245, 161, 130), (245, 160, 129), (245, 158, 127), (244, 157, 126), (244, 155, 124), (244, 154, 123),
+    (243, 152, 121), (243, 150, 120), (243, 149, 118), (242, 147, 117), (242, 145, 115), (241, 144, 114), (241, 142, 112), (240, 141, 111),
+    (240, 139, 109), (239, 137, 108), (238, 135, 106), (238, 134, 105), (237, 132, 103), (236, 130, 102), (236, 128, 100), (235, 127, 99),
+    (234, 125, 97), (234, 123, 96), (233, 121, 94), (232, 119, 93), (231, 117, 92), (230, 116, 90), (230, 114, 89), (229, 112, 87),
+    (228, 110, 86), (227, 108, 84), (226, 106, 83), (225, 104, 82), (224, 102, 80), (223, 100, 79), (222, 98, 78), (221, 96, 76),
+    (220, 94, 75), (219, 92, 74), (218, 90, 72), (217, 88, 71), (216, 86, 70), (215, 84, 68), (214, 82, 67), (212, 79, 66),
+    (211, 77, 64), (210, 75, 63), (209, 73, 62), (207, 70, 61), (206, 68, 60), (205, 66, 58), (204, 63, 57), (202, 61, 56),
+    (201, 59, 55), (200, 56, 53), (198, 53, 52), (197, 50, 51), (196, 48, 50), (194, 45, 49), (193, 42, 48), (191, 40, 46),
+    (190, 35, 45), (188, 31, 44), (187, 26, 43), (185, 22, 42), (184, 17, 41), (182, 13, 40), (181, 8, 39), (179, 3, 38),
+)
+CMAPS = {"coolwarm": COOLWARM_U8}
+CMAP_BAD_U8 = (0, 0, 0)                 # matplotlib's "bad" colour (0, 0, 0, 0) behind `[:3]`: what a NaN pixel gets
+
+
+def cmap_bytes(cmap):
+    """A colour map as a tuple of 256 (r, g, b) byte triples: a name of CMAPS, or any (256, 3) uint8 table (an ndarray, a
+    tensor or nested sequences) — e.g. `(plt.get_cmap(name)(np.arange(256))[:, :3] * 255).astype(np.uint8)`."""
+    if isinstance(cmap, str):
+        if cmap not in CMAPS:
+            raise ValueError("colour map %r is not built in (%s): pass its (256, 3) uint8 table" % (cmap, ", ".join(sorted(CMAPS))))
+        return CMAPS[cmap]
+    dtype = getattr(cmap, "dtype", None)
+    if dtype is not None and str(dtype) not in ("uint8", "torch.uint8"):
+        raise ValueError("a colour-map table must be uint8, got %s" % (dtype,))
+    rows = cmap.tolist() if hasattr(cmap, "tolist") else cmap
+    try:
+        rows = tuple(tuple(v for v in row) for row in rows)
+    except TypeError:
+        raise ValueError("a colour map is a name or a (256, 3) uint8 table, got %r" % (type(cmap).__name__,))
+    if len(rows) != 256 or any(len(row) != 3 for row in rows):
+        raise ValueError("a colour-map table must be (256, 3)")
+    if any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 255 for row in rows for v in row):
+        raise ValueError("a colour-map table must hold bytes")
+    return rows
+
+
+def cmap_table(cmap):
+    """What dd_attn_heat takes as `table`: (257, 4) float32 on the host, row k = colour byte / 255 of index k with torch's
+    own float32 division (the quotient dd_image_resample_u8's quantiser returns the byte for), row 256 the NaN colour,
+    the fourth column unused."""
+    rows = cmap_bytes(cmap) + (CMAP_BAD_U8,)
+    out = torch.zeros((257, 4), dtype=torch.float32)
+    out[:, :3] = torch.tensor(rows, dtype=torch.float32).div(255)
+    return out
+
+
+def device_cmap_table(cmap, device):
+    """cmap_table on `device` (_consts.device_const), keyed by the name or by the table's bytes."""
+    key = cmap if isinstance(cmap, str) else cmap_bytes(cmap)
+    return device_const(("attn_cmap", key), device, lambda: cmap_table(key))
+
+
 def png_capacity(h, w, channels=3):
     """The longest file of an (h, w) frame of 3 (RGB) or 4 (RGBA) channels: every chunk stored.  No content makes a file
     longer."""

@@ -1,6 +1,8 @@
 """Cross-attention maps of the text / camera / box context — the `cross_attn_map` of the reference's explore pipeline
 (pipeline/explore_pipeline_bev_controlnet.py:352-354,437-453,494-500,576; saved by tools/explore_unet.py:224-232 and
-turned into per-token heat maps by tools/explore_attn.py:97-151).
+turned into per-token heat maps by tools/explore_attn.py:97-151: `mean_map` below is its `gather_layer`, and
+pipeline/attn_output.py's `AttnMapRender` makes its pictures, `view_images_{view}.png` / `view_images_{view}box.png`, on
+the device from this capture).
 
 The reference gets them by installing a processor that calls `attn.get_attention_scores` on every `attn2` layer
 (tools/unet_modify.py:7-57) and keeps the conditional CFG half (`chunk(2)[1]`).  Here a `CrossAttnMapCapture` OBSERVES

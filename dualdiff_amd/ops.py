@@ -1120,6 +1120,85 @@ def map_compose_u8(src, index=None, legend=None, side="right"):
     return out
 
 
+def attn_heat(maps, cols, table, hw, out=None):
+    """The selected context columns of an attention map -> one coloured tile per (view, column), in one launch (include/
+    dualdiff_hip.h: dd_attn_heat; tools/explore_attn.py:118-128, 138-148).  maps (views, h * w, n) float32 with unit
+    stride along n — any row pitch >= n and any view stride, so a slice of a padded buffer is taken as it is; cols (t,)
+    int32, each in [0, n); table (257, 4) float32 (image_tables.cmap_table) — device tensors.
+    -> img (views * t, 3, h, w) float32 holding colour / 255: what image_resample_u8 quantises back to the colour bytes.
+    Nothing is read back."""
+    what = "attn_heat"
+    try:
+        h, w = (int(v) for v in hw)
+    except (TypeError, ValueError):
+        raise ValueError("%s: hw must be (h, w), got %r" % (what, hw))
+    if h <= 0 or w <= 0:
+        raise ValueError("%s: hw must be positive, got %r" % (what, hw))
+    if maps.dim() != 3 or maps.numel() == 0 or maps.shape[1] != h * w:
+        raise ValueError("%s takes maps (views, %d, n) for hw %s, got %s" % (what, h * w, (h, w), tuple(maps.shape)))
+    if maps.dtype != torch.float32:
+        raise ValueError("%s takes float32 maps, got %s" % (what, maps.dtype))
+    views, q, n = maps.shape
+    if maps.stride(2) != 1 or maps.stride(1) < n or maps.stride(0) < 0:
+        raise ValueError("%s takes maps with unit stride along n and a row pitch >= n, got strides %s"
+                         % (what, maps.stride()))
+    if cols.dtype != torch.int32 or cols.dim() != 1 or cols.numel() == 0 or not cols.is_contiguous():
+        raise ValueError("%s: cols must be a non-empty contiguous int32 vector, got %s %s"
+                         % (what, cols.dtype, tuple(cols.shape)))
+    if table.dtype != torch.float32 or tuple(table.shape) != (257, 4) or not table.is_contiguous():
+        raise ValueError("%s: table must be contiguous float32 (257, 4), got %s %s" % (what, table.dtype, tuple(table.shape)))
+    t = cols.shape[0]
+    if views * t > 65535:
+        raise ValueError("%s: at most 65535 tiles per launch, got %d x %d" % (what, views, t))
+    shape = (views * t, 3, h, w)
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise ValueError("%s: out must be a contiguous float32 %s tensor" % (what, shape))
+    _need_gpu(maps, cols, table, out)
+    img = torch.empty(shape, dtype=torch.float32, device=maps.device) if out is None else out
+    lib = _native.load()
+    _timer.launch(what, lib.dd_attn_heat, _ptr(maps), _ptr(cols), _ptr(table), _ptr(img), views, h, w, n, t,
+                  maps.stride(1), maps.stride(0), _stream(),
+                  book=lambda: ("dd_attn_heat_kernel", 0.0, float(views * t * q * (2 * 4 + 12))))
+    return img
+
+
+def attn_sheet_u8(tiles, index, rows, cols, gap, labels=None, out=None):
+    """view_images' canvas (tools/explore_attn.py:25-53) for a batch of sheets, in one launch (dd_attn_sheet_u8).  tiles
+    (m, th, tw, 3) uint8; index (sheets, rows * cols) int32: the tile of every cell in row-major order, -1 for an all-255
+    cell; gap: the gutter in pixels; labels (m, lh, tw, 3) uint8 or None: pasted over the bottom lh rows of the tile of
+    the same number — contiguous device tensors.
+    -> (sheets, rows * th + gap * (rows - 1), cols * tw + gap * (cols - 1), 3) uint8, 255 wherever no tile lies."""
+    what = "attn_sheet_u8"
+    if tiles.dim() != 4 or tiles.shape[3] != 3 or tiles.numel() == 0 or tiles.dtype != torch.uint8:
+        raise ValueError("%s takes uint8 tiles (m, th, tw, 3), got %s %s" % (what, tiles.dtype, tuple(tiles.shape)))
+    ints = (rows, cols, gap)
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in ints) or rows <= 0 or cols <= 0 or gap < 0:
+        raise ValueError("%s: rows and cols must be positive ints and gap a non-negative one, got %r" % (what, ints))
+    if index.dtype != torch.int32 or index.dim() != 2 or index.shape[0] == 0 or index.shape[1] != rows * cols:
+        raise ValueError("%s: index must be int32 (sheets, %d), got %s %s" % (what, rows * cols, index.dtype, tuple(index.shape)))
+    m, th, tw = tiles.shape[0], tiles.shape[1], tiles.shape[2]
+    sheets, lh = index.shape[0], 0
+    if labels is not None:
+        if labels.dim() != 4 or labels.dtype != torch.uint8 or labels.shape[0] != m or labels.shape[2:] != (tw, 3) \
+                or not 0 < labels.shape[1] <= th:
+            raise ValueError("%s: labels must be uint8 (%d, lh <= %d, %d, 3), got %s %s"
+                             % (what, m, th, tw, labels.dtype, tuple(labels.shape)))
+        lh = labels.shape[1]
+    ins = (tiles, index, labels)
+    if any(x is not None and not x.is_contiguous() for x in ins):
+        raise ValueError("%s takes contiguous tensors" % what)
+    oh, ow = rows * th + gap * (rows - 1), cols * tw + gap * (cols - 1)
+    if sheets > 65535 or oh * ow >= 1 << 31:
+        raise ValueError("%s: at most 65535 sheets of less than 2^31 pixels, got %d of %d x %d" % (what, sheets, oh, ow))
+    out = _image_out(out, (sheets, oh, ow, 3), tiles.device, what)
+    _need_gpu(*ins, out)
+    lib = _native.load()
+    _timer.launch(what, lib.dd_attn_sheet_u8, _ptr(tiles), _ptr(index), _ptr(labels), _ptr(out), m, sheets, rows, cols, th,
+                  tw, lh, gap, _stream(),
+                  book=lambda: ("dd_attn_sheet_kernel", 0.0, float(2 * out.numel())))
+    return out
+
+
 def groupnorm(x, gamma, beta, m, hw, groups, eps, silu, x2=None, out=None):
     """GroupNorm (+SiLU) over an NHWC batch; x2 = optional second source concatenated on C."""
     lib = _native.load()

@@ -314,6 +314,49 @@ int dd_attn_probs(const void* q, const void* k, float* p, int64_t ldq, int64_t l
                   float weight, const int32_t* lk_dev, int32_t qk_dtype, dd_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Attention-map pictures (csrc/attn_heat.hip): the per-token heat-map sheets the reference's analysis script makes of
+ * the averaged map, `view_images_{view}.png` and `view_images_{view}box.png` (tools/explore_attn.py:114-151, with
+ * text_under_image :13-23 and view_images :25-53).  Between the two entry points lies dd_image_resample_u8 (PIL's
+ * bicubic resize of :129 / :149, its bottom pad the white strip of :15-16): three launches, no host synchronisation.
+ *
+ * dd_attn_heat: normalise and colour the selected context columns (:118-128, :138-148), one launch.
+ *   maps   float [views][q][ldm] (device), q = h * w: element (v, r, j) at v * view_stride + r * ldm + j (elements),
+ *          ldm >= n.  Only 4-byte alignment is asked, so a buffer with a padded pitch and a contiguous one both do.
+ *   cols   int32 [t] (device): the columns to draw, each in [0, n) (clamped to it: nothing else is ever read).
+ *   table  float [257][4] (device): per colour-map index {r / 255, g / 255, b / 255, unused}; row 256 is the NaN colour
+ *          (matplotlib's "bad" colour, black).
+ *   img    float [views * t][3][h][w]: tile v * t + i is column cols[i] of view v, as colour / 255.  The quotients are
+ *          the caller's, so that dd_image_resample_u8 quantises them back to the colour bytes.
+ *   Arithmetic, per (view, column): the exact minimum and maximum of the column over the q rows; per pixel
+ *          X = (double(x) - double(min)) / (double(max) - double(min)) in IEEE fp64 (:120-122, with np.float64 for the
+ *          removed np.float), k = min(int(X * 256.0), 255), and k = 256 where X is NaN (a constant column: 0 / 0) —
+ *          matplotlib's Colormap.__call__ on a float in [0, 1] (:123-127).  float32 subnormals and signed zeros convert
+ *          to double exactly (the double is built from the bits; the extrema are found by integer compares).  A
+ *          non-finite input gives an unspecified colour; the index is clamped to the table.
+ *   No atomics, identical bits from run to run.
+ * DD_ERR_BAD_ARG, before any runtime call: a NULL maps / cols / table / img, views / h / w / n / t <= 0, ldm < n, a
+ * negative view_stride, a pointer that is not 4-byte aligned.  views * t > 65535 or h * w >= 2^31: DD_ERR_UNSUPPORTED.
+ *
+ * dd_attn_sheet_u8: view_images' canvas (:25-53) for `sheets` sheets of rows x cols cells, one launch.
+ *   tiles  uint8 [m][th][tw][3] (device): the resized tiles (dd_image_resample_u8's output, strip included);
+ *   index  int32 [sheets][rows * cols] (device): the tile of each cell, row-major (:46-49); -1 (anything outside
+ *          [0, m)) is an all-255 cell, the reference's "empty" image;
+ *   labels uint8 [m][lh][tw][3] (device): pasted over the bottom lh rows of the tile of the same number
+ *          (text_under_image's strip, :13-23), or NULL with lh == 0;
+ *   gap    the gutter between cells, int(tile height * offset_ratio) of :39;
+ *   out    uint8 [sheets][rows * th + gap * (rows - 1)][cols * tw + gap * (cols - 1)][3], 255 in the gutters (:44-45).
+ *          Every byte is written exactly once, no alignment is asked of it.
+ * DD_ERR_BAD_ARG, before any runtime call: a NULL tiles / index / out, m / sheets / rows / cols / th / tw <= 0, lh or
+ * gap < 0, labels without lh or lh without labels, lh > th, a misaligned index.  sheets > 65535, or a sheet of 2^31
+ * pixels or more (th + gap and tw + gap included): DD_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------- */
+int dd_attn_heat(const float* maps, const int32_t* cols, const float* table, float* img, int32_t views, int32_t h,
+                 int32_t w, int32_t n, int32_t t, int64_t ldm, int64_t view_stride, dd_stream_t stream);
+int dd_attn_sheet_u8(const uint8_t* tiles, const int32_t* index, const uint8_t* labels, uint8_t* out, int32_t m,
+                     int32_t sheets, int32_t rows, int32_t cols, int32_t th, int32_t tw, int32_t lh, int32_t gap,
+                     dd_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Fused cross-attention of the 320-channel level (8 heads x 40, <= 128 context keys per view-instance), ONE launch:
  *   out[r, :] = ( softmax_j( scale * (x[r] Wq^T)_h . K[i, j]_h ) V[i, j]_h )_h Wo^T + bo + res[r, :]
  * for query row r of view-instance i = r / rows_per_inst; optionally also ln_out = LayerNorm(out) (two-pass fp32
