@@ -31,14 +31,24 @@ SIBLING_OVERLAP = os.environ.get("DD_SIBLING_OVERLAP", "1") != "0"
 # storages of forward-graph OUTPUT buffers: a replay rewrites them without any version count (`graph_forward = "alias"` hands
 # them to the caller), so they can never be vouched for
 _STATIC_STORAGE = set()
-_SIB = __import__("threading").local()           # .window: the latest forward() entry on this thread
+_SIB = __import__("threading").local()           # .window: the latest forward() entry on this thread; .speculative: below
 _SIB_HOLD_BYTES = (64 << 20, 192 << 20)          # per tensor / per entry: larger inputs are not held (and never proven ready)
+_SIB_GEN = [0]                                   # sibling_barrier() count: an entry made before the latest one vouches for nothing
+_SIB_SHARE_GEN = [0]                             # ModelBase._invalidate() count: which models share weights is looked at again
+
+
+class _NotRecorded(Exception):
+    """Raised by ForwardGraphs.call on the side stream, before it has launched or changed anything, when the call would
+    not replay a recorded graph: sibling_overlap runs it again on the caller's stream."""
 
 
 def sibling_barrier():
-    """Forget the latest forward() entry of this thread: called by code of this package that rewrites tensors through raw
-    pointers outside the public forward()s (the fused sampler's step), so that nothing it touched can be vouched for."""
+    """Forget every forward() entry made so far (this thread's window at once, the entries other threads and the models
+    themselves still hold through the count): called by whatever changes memory that a later forward() reads and that no
+    version count describes — the fused sampler's step, which rewrites its buffers through raw pointers, and
+    ModelBase._invalidate, i.e. every change of a model's weights."""
     _SIB.window = None
+    _SIB_GEN[0] += 1
 
 
 def _flat_tensors(obj, out):
@@ -82,8 +92,15 @@ class _Seen:
             self.items[idv[0]] = (t, idv[1])
         self.owner = weakref.ref(owner)
         self.stream = (stream.device_index, stream.cuda_stream)
+        self.state = (_layers.CACHE_EPOCH[0], _SIB_GEN[0])
         self.event = torch.cuda.Event()
         self.event.record(stream)
+
+    def current(self):
+        """No packed weight was dropped (layers.CACHE_EPOCH: .to() / load_state_dict / fold_lora_ / enable_fp8_weights, on
+        a sub-module alone too) and no sibling_barrier() was called since this entry: whatever did that is enqueued
+        BEHIND this entry's event, and the next forward() has to run behind it."""
+        return self.state == (_layers.CACHE_EPOCH[0], _SIB_GEN[0])
 
     def vouches(self, t):
         idv = _ident(t)
@@ -91,6 +108,27 @@ class _Seen:
             return False
         held = self.items.get(idv[0])
         return held is not None and held[1] == idv[1] and held[0]._version == idv[1]
+
+
+def _shares_weights(a, b):
+    """Two models that hold the same sub-module object or the same parameter / buffer memory (one bbox_embedder in both
+    ControlNets, say).  Such a pair is never overlapped: a shared module's host-side caches (layers.derived) and whatever
+    scratch it owns know nothing of streams.  Walked once per pair; forgotten with any packed-weight drop (CACHE_EPOCH) and
+    any model's _invalidate()."""
+    state = (_layers.CACHE_EPOCH[0], _SIB_SHARE_GEN[0])
+    cache = a.__dict__.get("_sib_shares")
+    if cache is None or cache[0] != state:
+        cache = a.__dict__["_sib_shares"] = (state, {})
+    hit = cache[1].get(id(b))
+    if hit is None or hit[0]() is not b:
+        def footprint(model):
+            mods = {id(m) for m in model.modules() if m is not model}
+            mem = {t.untyped_storage().data_ptr() for t in list(model.parameters()) + list(model.buffers())}
+            mem.discard(0)
+            return mods, mem
+        (ma, sa), (mb, sb) = footprint(a), footprint(b)
+        hit = cache[1][id(b)] = (weakref.ref(b), bool(ma & mb) or bool(sa & sb))
+    return hit[1]
 
 
 def sibling_overlap(fwd):
@@ -108,7 +146,24 @@ def sibling_overlap(fwd):
     extension writing through raw pointers, which this cannot see — must not be relied on; the former is refused.
     Anything else — a new tensor (say, one computed from the sibling's outputs), an in-place update since (version),
     tensors too large to hold, inference tensors, alias outputs, eager or sharded models, a capture in progress — takes
-    the ordinary path.  Results are bit-identical either way (tests/test_forward_graphs_gpu.py)."""
+    the ordinary path.  Results are bit-identical either way (tests/test_forward_graphs_gpu.py).
+
+    The arguments are not all a forward() reads, and torch is not the only writer, so the rule goes on
+    (tests/test_sibling_overlap_gpu.py; tests/sibling_cases.py restates it as a pure-Python model):
+      - only a REPLAY of a graph already recorded in the current epoch is overlapped.  The call is moved on that
+        expectation and ForwardGraphs.call, before it launches anything, raises _NotRecorded for everything else (first
+        sight, capture, stale epoch, eager-only key, an input that stopped aliasing); the call then runs again on the
+        caller's stream.  Weight packing, tile tuning and captures never run beside a sibling or ahead of the caller's work;
+      - an entry made before a packed-weight drop (layers.CACHE_EPOCH) or a sibling_barrier() vouches for nothing, and
+        ModelBase._invalidate — every sanctioned change of a model's weights — calls the barrier: the copies that change the
+        weights are enqueued on the caller's stream behind that entry's event;
+      - this package's own raw-pointer writers count versions like torch's in-place ops (ops._written);
+      - two models that share a sub-module object or parameter memory are never overlapped with each other
+        (_shares_weights): host-side caches of packed weights know nothing of streams;
+      - the caller's stream joins the side stream also when fwd raises, and the window is cleared then.
+    Invisible by construction, and so the caller's to announce with sibling_barrier() (or DD_SIBLING_OVERLAP=0): writes
+    through `tensor.data`, which counts versions of its own; a foreign extension writing through raw pointers; parameters
+    rewritten without _invalidate() — a replay keeps reading the packed copies it was recorded with, as it always did."""
     import functools
 
     @functools.wraps(fwd)
@@ -125,21 +180,40 @@ def sibling_overlap(fwd):
         window, mine = getattr(_SIB, "window", None), self.__dict__.get("_sib_prev")
         _SIB.window = entry
         self.__dict__["_sib_prev"] = entry
-        ok = window is not None and window.stream == here and window.owner() is not self \
-            and window.owner() is not None and len(tensors) > 0
+        other = window.owner() if window is not None else None
+        ok = other is not None and other is not self and window.stream == here and window.current() and len(tensors) > 0
         if ok:
-            mine_ok = mine is not None and mine.stream == here
-            ok = all(window.vouches(t) or (mine_ok and mine.vouches(t)) for t in tensors)
+            mine_ok = mine is not None and mine.stream == here and mine.current()
+            ok = all(window.vouches(t) or (mine_ok and mine.vouches(t)) for t in tensors) \
+                and not _shares_weights(self, other)
+        if ok:
+            side = self.__dict__.get("_sib_stream")
+            if side is None:
+                side = self.__dict__["_sib_stream"] = torch.cuda.Stream()
+            side.wait_event(window.event)
+            from .. import ops as _ops
+            done = False
+            try:
+                # ForwardGraphs.call takes the flag back and raises _NotRecorded unless it is about to replay: the first
+                # sight of a key (eager: weight packing, tile tuning) and its capture belong on the caller's stream, behind
+                # whatever the caller enqueued — only a replay reads nothing but its arguments and what the graph owns
+                _SIB.speculative = True
+                with torch.cuda.stream(side), _ops.workspace_owner(("sibling", id(self))):
+                    out = fwd(self, *args, **kwargs)
+                done = True
+            except _NotRecorded:
+                ok = False
+            finally:
+                _SIB.speculative = False
+                cur.wait_stream(side)
+                if not done and ok:                      # fwd raised: nothing of this entry may be relied on
+                    _SIB.window = None
         if not ok:
-            return fwd(self, *args, **kwargs)
-        side = self.__dict__.get("_sib_stream")
-        if side is None:
-            side = self.__dict__["_sib_stream"] = torch.cuda.Stream()
-        side.wait_event(window.event)
-        from .. import ops as _ops
-        with torch.cuda.stream(side), _ops.workspace_owner(("sibling", id(self))):   # its eager launches: own scratch too
-            out = fwd(self, *args, **kwargs)
-        cur.wait_stream(side)
+            try:
+                return fwd(self, *args, **kwargs)
+            except BaseException:
+                _SIB.window = None
+                raise
         res = out.to_tuple() if hasattr(out, "to_tuple") else (out.sample if hasattr(out, "sample") else out)
         for t in _flat_tensors(res, []):
             t.record_stream(cur)
@@ -215,7 +289,13 @@ class ForwardGraphs:
         """tensors: flat list of tensors / None; impl(list) -> flat list of output tensors.  alias_out: return views of
         the graph's static output buffers instead of copies."""
         key = (key, tuple(None if t is None else (tuple(t.shape), t.dtype, tuple(t.stride())) for t in tensors))
+        # sibling_overlap moved this forward() to the model's side stream on the expectation of a replay: anything else
+        # (an eager-only key, a first sight, a capture, a stale epoch, an input that no longer aliases) goes back to the
+        # caller's stream — decided here, where the path is chosen, before anything is launched
+        speculative, _SIB.speculative = getattr(_SIB, "speculative", False), False
         if key in self.eager_only:
+            if speculative:
+                raise _NotRecorded()
             return impl(list(tensors))
         e = self.entries.get(key)
         if e is not None and e["epoch"] != _layers.CACHE_EPOCH[0]:
@@ -231,8 +311,10 @@ class ForwardGraphs:
                     break
                 dst.append(st)
                 src.append(t)
-            if e is not None and dst:             # one multi-tensor launch per dtype group instead of one copy per input
-                torch._foreach_copy_(dst, src, non_blocking=True)
+        if e is None and speculative:
+            raise _NotRecorded()
+        if e is not None and dst:                 # one multi-tensor launch per dtype group instead of one copy per input
+            torch._foreach_copy_(dst, src, non_blocking=True)
         if e is None:
             if key not in self.seen and key not in self.no_alias:
                 if len(self.seen) > 64:
@@ -336,6 +418,10 @@ class ModelBase(nn.Module):
         self.__dict__["_temb_bank"] = self.__dict__["_kv_bank"] = None         # with their stacked matrices
         if self.__dict__.get("_fwd_graphs") is not None:
             self.__dict__["_fwd_graphs"].clear()
+        # the caller is changing this model's weights on its stream: the next forward() runs behind that, not behind an
+        # earlier entry's event
+        _SIB_SHARE_GEN[0] += 1
+        sibling_barrier()
 
     # -- HIP graphs behind forward() -----------------------------------------------------------
     graph_forward = True        # True: graphs, outputs copied out (safe default); "alias": graphs, outputs are views of

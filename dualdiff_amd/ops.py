@@ -74,14 +74,28 @@ def _forget_derived(t):
             delattr(t, a)
 
 
+def _written(*ts):
+    """Counts a version on every tensor of the CALLER's that a kernel is about to write through its data pointer, as
+    torch does for its own in-place ops: `tensor._version` is what tells a reader that the bytes changed
+    (model_base.sibling_overlap proves with it that an argument was ready before an earlier point of the stream;
+    layers.derived keys packed weights on it).  Only a host counter — nothing is launched, also inside a stream capture.
+    Tensors the wrapper allocated itself need none (nobody has seen them), inference tensors count none (and are never
+    vouched for).  tests/sibling_cases.py lists every wrapper that must come through here."""
+    for t in ts:
+        if t is not None and not t.is_inference():
+            torch.autograd.graph.increment_version(t)
+
+
 def _out_or_new(out, shape, dtype, device, what):
     """The tensor a wrapper writes: a fresh one (`shape` may be a tensor whose layout it takes: torch.empty_like), or
-    the caller's `out` — of the dtype the kernel stores, and without the attributes that described its old contents."""
+    the caller's `out` — of the dtype the kernel stores, without the attributes that described its old contents, and
+    one version on."""
     if out is None:
         return torch.empty_like(shape) if isinstance(shape, torch.Tensor) else torch.empty(shape, dtype=dtype, device=device)
     if out.dtype != dtype:
         raise TypeError("%s: out must be %s" % (what, dtype))
     _forget_derived(out)
+    _written(out)
     return out
 
 
@@ -154,7 +168,8 @@ def gemm(a, w, bias=None, *, a2=None, res=None, rowvec=None, rows_per_inst=1, al
             raise ValueError("head_major needs a plain epilogue, its own output and n % D == 0")
         hm_out = torch.empty((n // hd, rows, hd), dtype=a.dtype, device=a.device)
         out = hm_out.view(rows, n)           # same bytes; the kernel ignores ldc in this mode
-    out = _out_or_new(out, (rows, n), odt, a.device, "gemm")
+    else:
+        out = _out_or_new(out, (rows, n), odt, a.device, "gemm")
     d = GemmDesc()
     d.out_f32 = int(bool(out_f32))
     if hm_out is not None:
@@ -357,6 +372,7 @@ def _image_out(out, shape, device, what):
         return torch.empty(shape, dtype=torch.uint8, device=device)
     if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
         raise ValueError("%s: out must be a contiguous uint8 %s tensor" % (what, tuple(shape)))
+    _written(out)
     return out
 
 
@@ -465,6 +481,8 @@ def image_load_u8(frames, size, box=None, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0
         out = torch.empty(shape, dtype=dtype, device=frames.device)
     elif out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
         raise ValueError("%s: out must be a contiguous %s %s tensor" % (what, dtype, shape))
+    else:
+        _written(out)
     _need_gpu(frames, out)
     _forget_derived(out)
     lib = _native.load()
@@ -505,6 +523,7 @@ def jpeg_encode_u8(frames, quality=75, out=None, capacity=None):
         if capacity is not None and int(capacity) != out.shape[1]:
             raise ValueError("%s: capacity %r does not match out %s" % (what, capacity, tuple(out.shape)))
         capacity = out.shape[1]
+        _written(out)
     capacity = header_len + max(h * w, 2) if capacity is None else int(capacity)        # 1 x 1: room for the end marker
     if capacity < header_len + 2:
         raise ValueError("%s: capacity must be at least the header and the end marker (%d bytes), got %d"
@@ -561,6 +580,7 @@ def _png_encode(what, channels, frames, out, capacity):
         if capacity is not None and int(capacity) != out.shape[1]:
             raise ValueError("%s: capacity %r does not match out %s" % (what, capacity, tuple(out.shape)))
         capacity = out.shape[1]
+        _written(out)
     capacity = png_capacity(h, w, ch) if capacity is None else int(capacity)
     if capacity < PNG_FILE_FIXED:
         raise ValueError("%s: capacity must be at least the fixed parts of a file (%d bytes), got %d"
@@ -727,6 +747,8 @@ def png_condition(frames, views=6, top=0, left=0, size=None, out=None):
         out = torch.empty(shape, dtype=torch.float32, device=frames.device)
     elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
         raise ValueError("%s: out must be a contiguous float32 %s tensor" % (what, shape))
+    else:
+        _written(out)
     _need_gpu(frames, out)
     _forget_derived(out)
     lib = _native.load()
@@ -775,6 +797,8 @@ def png_condition_resized(frames, views=6, pad_top=0, resize=None, top=0, left=0
         out = torch.empty(shape, dtype=torch.float32, device=frames.device)
     elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
         raise ValueError("%s: out must be a contiguous float32 %s tensor" % (what, shape))
+    else:
+        _written(out)
     _need_gpu(frames, out)
     if out.data_ptr() % 16:
         raise ValueError("%s: out must start on a 16-byte boundary" % what)
@@ -849,6 +873,7 @@ def box_views(corners, labels, offsets, transforms, views, cap, points_mode="all
                                 for t, s, d in zip(out, shapes, dtypes)):
             raise ValueError("%s: out must be contiguous tensors of %s" % (what, list(zip(shapes, dtypes))))
         _need_gpu(*out)
+        _written(*out)
     lib = _native.load()
     _timer.launch(what, lib.dd_box_views, _ptr(corners), _ptr(filter_corners), _ptr(labels), _ptr(offsets),
                   _ptr(transforms) if fm != 0 else None, total, scenes, views, cap, BOX_POINT_MODES[points_mode], fm, ch, cw,
@@ -1036,6 +1061,7 @@ def bev_map_layers(static, corners, bottom_center, height, visibility, labels, o
                                          or not aux.is_contiguous())):
             raise ValueError("%s: out must be (uint8 (%d, %d, %d, %d), fp32 (%d, %d, %d, %d) or None, int32 (1,))"
                              % (what, b, ns + nd, size, size, b, ch, size, size))
+        _written(masks, aux, flags)
     _need_gpu(workspace, masks, aux, flags)
     lib = _native.load()
     _native.check(lib.dd_bev_map_layers(_ptr(static), 1 if bits else 0, _ptr(corners), _ptr(bottom_center), _ptr(height),
@@ -1154,6 +1180,7 @@ def attn_heat(maps, cols, table, hw, out=None):
     if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous()):
         raise ValueError("%s: out must be a contiguous float32 %s tensor" % (what, shape))
     _need_gpu(maps, cols, table, out)
+    _written(out)
     img = torch.empty(shape, dtype=torch.float32, device=maps.device) if out is None else out
     lib = _native.load()
     _timer.launch(what, lib.dd_attn_heat, _ptr(maps), _ptr(cols), _ptr(table), _ptr(img), views, h, w, n, t,
@@ -1369,6 +1396,8 @@ def attention_probs(q, k, batch, lq, lk, heads, head_dim, scale=None, *, q_presc
         out = torch.empty(shape[:-1] + ((lk + 3) // 4 * 4,), dtype=torch.float32, device=q.device)[..., :lk]
     elif out.dtype != torch.float32:
         raise TypeError("attention_probs: out must be torch.float32")
+    else:
+        _written(out)
     _timer.launch("attention_probs", lib.dd_attn_probs, _ptr(q), _ptr(k), _ptr(out), qa[1], ka[1], qa[2], ka[2], qa[3],
                   ka[3], out.stride(-2), out.stride(0), out.stride(1) if per_head else 0, batch, lq, lk, heads, head_dim,
                   float(scale) if scale is not None else head_dim ** -0.5, int(bool(q_prescaled)), int(bool(per_head)),
@@ -1630,6 +1659,7 @@ def cfg_ddim_step(eps, x, coef, guidance, x_out=None, x_dup=None, given=None):
     given: None (the plain step) or a GivenViews — dd_cfg_ddim_step_given."""
     lib = _native.load()
     _need_gpu(eps, x, coef, x_out, x_dup)
+    _written(x_out, x_dup)
     if x_out is None:
         x_out = torch.empty_like(x)
     if given is None:
@@ -1653,6 +1683,7 @@ def cfg_unipc_step(eps, x, hist, coef, guidance, x_out=None, x_dup=None, given=N
     _need_gpu(eps, x, hist, coef, x_out, x_dup)
     if hist.dtype != torch.float32 or hist.shape[0] != 3 or hist[0].numel() != x.numel() or not hist.is_contiguous():
         raise ValueError("hist must be a contiguous fp32 (3, n...) tensor")
+    _written(x_out, x_dup, hist)
     if x_out is None:
         x_out = torch.empty_like(x)
     if given is None:
@@ -1677,6 +1708,7 @@ def given_views_noise(x, given, t0, x_dup=None):
     ve = _given_args(given, x)
     if x_dup is not None and (x_dup.dtype != x.dtype or x_dup.numel() != x.numel()):
         raise ValueError("x_dup must match x")
+    _written(x, x_dup)
     sa, s1a = (float(v) for v in t0.tolist()[:2])
     rc = lib.dd_given_views_noise(_ptr(x), _ptr(x_dup), _ptr(given.mask), _ptr(given.clean), _ptr(given.noise0),
                                   sa, s1a, x.numel(), ve, _dt(x), _stream())
@@ -1848,7 +1880,8 @@ def box_tokens(points, classes, masks, class_tokens, null_pos, null_class, freqs
                cls_out=None, normalize=None):
     """Both operands of the box MLP in one launch (include/dualdiff_hip.h: dd_box_tokens; bbox_embedder.py:164-203).
     points (rows, P, 3) fp16 / bf16 / fp32; classes (rows,) int64; masks (rows,) bool or None; pos (rows, P * 3 * (inc + 2
-    F)) and cat (rows, >= cls_offset + D) are written in place (dtype of class_tokens); normalize = (xyz_min, xyz_range)."""
+    F)) and cat (rows, >= cls_offset + D) are written in place (dtype of class_tokens), and cls_out where one is given;
+    normalize = (xyz_min, xyz_range)."""
     lib = _native.load()
     _need_gpu(points, classes, masks, class_tokens, null_pos, null_class, pos, cat, cls_out)
     rows, npts = points.shape[0], points.shape[1]
@@ -1866,6 +1899,7 @@ def box_tokens(points, classes, masks, class_tokens, null_pos, null_class, freqs
     if tuple(pos.shape) != (rows, npts * 3 * ((1 if include_input else 0) + 2 * nf)) or pos.dtype != class_tokens.dtype \
             or cat.dtype != class_tokens.dtype or cat.shape[0] != rows:
         raise ValueError("box_tokens: operand shapes / dtypes do not match")
+    _written(pos, cat, cls_out)
     d.points, d.classes, d.masks = points.data_ptr(), classes.data_ptr(), (masks.data_ptr() if masks is not None else None)
     d.class_tokens, d.null_pos, d.null_class = class_tokens.data_ptr(), null_pos.data_ptr(), null_class.data_ptr()
     d.pos, d.cat, d.cls_out = pos.data_ptr(), cat.data_ptr(), (cls_out.data_ptr() if cls_out is not None else None)
@@ -1974,7 +2008,8 @@ def gemm8(a8, a_scale, w8, w_scale, bias=None, *, res=None, out=None, head_major
         hm_out = torch.empty((n // hd, rows, hd), dtype=dtype, device=a8.device)
         out = hm_out.view(rows, n)
         d.out_headmajor_d, d.hm_scaled_planes, d.hm_scale = int(hd), int(hplanes), float(hscale)
-    out = _rows2d(_out_or_new(out, (rows, n // 2 if geglu else n), dtype if out is None else out.dtype, a8.device, "gemm8"))
+    else:
+        out = _rows2d(_out_or_new(out, (rows, n // 2 if geglu else n), dtype if out is None else out.dtype, a8.device, "gemm8"))
     d.a, d.a_scale, d.lda = a8.data_ptr(), a_scale.data_ptr(), a8.stride(0)
     d.w, d.w_scale, d.ldw = w8.data_ptr(), w_scale.data_ptr(), w8.stride(0)
     d.bias = bias.data_ptr() if bias is not None else None
@@ -2033,6 +2068,7 @@ def _slice_out(out, rows, cols, c_off, dtype, device, what):
         raise ValueError("%s: out %s cannot hold %d rows x columns %d..%d" % (what, tuple(out.shape), rows, c_off,
                                                                                c_off + cols))
     _forget_derived(out)
+    _written(out)
     return out
 
 
