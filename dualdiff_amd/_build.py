@@ -27,6 +27,9 @@ SOURCES = ["gemm23.hip", "gemm2_conv.hip", "attention.hip", "gemm1.hip", "conv3s
            "ors_render.hip",
            # the map input runs in the data path, before the first step: behind everything, for the same reason
            "bev_map.hip",
+           # the FGM loss mask runs in the data path and its loss once per training step, neither in a denoising step: behind
+           # everything, for the same reason.  No flag of its own below: its float64 projection must stay IEEE-rounded
+           "fgm_mask.hip",
            # the attention-map probe is launched only while a capture is installed: behind everything, for the same reason
            "attn_probs.hip",
            # the heat-map sheets are made of the captured maps after the last step: behind everything, for the same reason.

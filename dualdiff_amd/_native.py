@@ -154,6 +154,12 @@ SIGNATURES = {
     "dd_bev_map_layers": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_double, c_double, c_double,
                                     c_double, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dd_fgm_workspace_bytes": (c_int64, [c_int32]),
+    "dd_fgm_mask": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                              c_double, c_double, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "dd_fgm_loss_workspace_bytes": (c_int64, [c_int64]),
+    "dd_fgm_loss": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32,
+                              c_int32, c_int32, c_void_p]),
     "dd_fourier_embed": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, POINTER(c_float), c_int32, c_int32,
                                    c_int32, c_int32, c_void_p]),
     "dd_conv3x3_small_cout": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,

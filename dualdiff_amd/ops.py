@@ -1071,6 +1071,106 @@ def bev_map_layers(static, corners, bottom_center, height, visibility, labels, o
     return masks, aux, flags
 
 
+FGM_MAX_POINTS, FGM_MAX_PIXELS, FGM_REC_WORDS = 8, 1 << 20, 24     # csrc/fgm_mask_core.h, include/dualdiff_hip.h
+FGM_REC_NV, FGM_REC_FLAGGED, FGM_REC_WEIGHT, FGM_REC_AREA, FGM_REC_BBOX = 16, 17, 18, 19, 20
+FGM_LOSS_DTYPES = {torch.float16: DD_F16, torch.bfloat16: DD_BF16, torch.float32: _native.DD_F32}
+
+
+def fgm_workspace_bytes(total):
+    n = _native.load().dd_fgm_workspace_bytes(int(total))
+    if n < 0:
+        raise _native.Unsupported("dualdiff_amd.fgm_mask: %d boxes are more than one call takes" % total)
+    return n
+
+
+def fgm_mask(bboxes, masks, lidar2image, resolution, crop=None, scale=None, *, workspace=None):
+    """The FGM loss mask of a batch in two launches (include/dualdiff_hip.h: dd_fgm_mask; networks/utils.py:26-39, 100-163
+    and hd_crop, dataset/utils.py:348-353).  bboxes (b, n, m, P, 3) fp32 with P <= 8, masks (b, n, m) bool or uint8,
+    lidar2image (b, n, 4, 4) fp32 — contiguous device tensors; resolution = (W, H) of the latent grid; crop = (H_out, W_out)
+    or None; scale = (sx, sy), default (W / 1600, H / 900).  workspace: a uint8 device tensor of at least
+    fgm_workspace_bytes(b * n * m) bytes, 16-byte aligned (default: a new one); after the call it holds the box records.
+    -> (heat (b, n, H_out, W_out) fp32, flags (1,) int32: the number of unsupported boxes).  Nothing is read back."""
+    what = "fgm_mask"
+    try:
+        width, height = (int(v) for v in resolution)
+        ho, wo = (height, width) if crop is None else (int(v) for v in crop)
+        sx, sy = (width / 1600, height / 900) if scale is None else (float(v) for v in scale)
+    except (TypeError, ValueError):
+        raise ValueError("%s: resolution = (W, H), crop = (H_out, W_out), scale = (sx, sy), got %r, %r, %r"
+                         % (what, resolution, crop, scale))
+    if width < 1 or height < 1 or width * height > FGM_MAX_PIXELS:
+        raise ValueError("%s: the grid must be at least 1 x 1 and at most %d pixels, got %d x %d"
+                         % (what, FGM_MAX_PIXELS, width, height))
+    if not (1 <= wo <= width and 1 <= ho <= height) or (width - wo) % 2:
+        raise ValueError("%s: the crop (%d, %d) must fit the grid (%d, %d) and leave an even number of columns"
+                         % (what, ho, wo, height, width))
+    if bboxes.dim() != 5 or bboxes.shape[4] != 3 or not 1 <= bboxes.shape[3] <= FGM_MAX_POINTS or bboxes.dtype != torch.float32:
+        raise ValueError("%s takes fp32 bboxes (b, n, m, P <= %d, 3), got %s %s"
+                         % (what, FGM_MAX_POINTS, bboxes.dtype, tuple(bboxes.shape)))
+    b, n, m, points = bboxes.shape[:4]
+    if masks.dtype not in (torch.bool, torch.uint8) or tuple(masks.shape) != (b, n, m):
+        raise ValueError("%s takes bool masks (%d, %d, %d), got %s %s" % (what, b, n, m, masks.dtype, tuple(masks.shape)))
+    if lidar2image.dtype != torch.float32 or tuple(lidar2image.shape) != (b, n, 4, 4):
+        raise ValueError("%s takes fp32 lidar2image (%d, %d, 4, 4), got %s %s"
+                         % (what, b, n, lidar2image.dtype, tuple(lidar2image.shape)))
+    if b * n < 1:
+        raise ValueError("%s: no view in bboxes %s" % (what, tuple(bboxes.shape)))
+    ins = (bboxes, masks, lidar2image)
+    if any(not t.is_contiguous() for t in ins):
+        raise ValueError("%s takes contiguous tensors" % what)
+    _need_gpu(*ins)
+    dev = bboxes.device
+    need = fgm_workspace_bytes(b * n * m)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
+        raise ValueError("%s: the workspace must be a contiguous uint8 tensor of at least %d bytes" % (what, need))
+    else:
+        _written(workspace)
+    _need_gpu(workspace)
+    heat = torch.empty((b, n, ho, wo), dtype=torch.float32, device=dev)
+    flags = torch.empty((1,), dtype=torch.int32, device=dev)
+    lib = _native.load()
+    _native.check(lib.dd_fgm_mask(_ptr(bboxes), _ptr(masks), _ptr(lidar2image), b * n, m, points, width, height, wo, ho,
+                                  sx, sy, _ptr(workspace), workspace.numel(), _ptr(heat), _ptr(flags), _stream()), what)
+    return heat, flags
+
+
+def fgm_loss_groups(count):
+    """the workgroups of dd_fgm_loss's first launch (include/dualdiff_hip.h: a function of the element count alone)"""
+    return max(1, min((int(count) + 1023) // 1024, 1024))
+
+
+def fgm_loss(pred, target, heat=None, want_grad=False):
+    """sum((pred - target)^2 * (1 + heat)) / N in fp32 and, with want_grad, its gradient to pred in pred's dtype, in one
+    pass over the inputs plus one workgroup over the partials (include/dualdiff_hip.h: dd_fgm_loss; runner/
+    multiview_runner.py:501-507).  pred, target (b, n, c, h, w) fp16 / bf16 / fp32, heat (b, n, h, w) fp32 or None (the plain
+    mean) — contiguous device tensors.  -> (loss () fp32, grad or None).  Nothing is read back."""
+    what = "fgm_loss"
+    if pred.dtype not in FGM_LOSS_DTYPES:
+        raise TypeError("%s takes fp16 / bf16 / fp32 tensors, got %s" % (what, pred.dtype))
+    if pred.dim() != 5 or pred.numel() == 0 or target.shape != pred.shape or target.dtype != pred.dtype:
+        raise ValueError("%s takes pred and target of one shape (b, n, c, h, w) and dtype, got %s %s and %s %s"
+                         % (what, pred.dtype, tuple(pred.shape), target.dtype, tuple(target.shape)))
+    b, n, c, h, w = pred.shape
+    if heat is not None and (heat.dtype != torch.float32 or tuple(heat.shape) != (b, n, h, w)):
+        raise ValueError("%s takes fp32 heat (%d, %d, %d, %d), got %s %s" % (what, b, n, h, w, heat.dtype, tuple(heat.shape)))
+    ins = (pred, target, heat)
+    if any(t is not None and not t.is_contiguous() for t in ins):
+        raise ValueError("%s takes contiguous tensors" % what)
+    _need_gpu(*ins)
+    lib = _native.load()
+    need = lib.dd_fgm_loss_workspace_bytes(pred.numel())
+    if need < 0:
+        raise _native.Unsupported("dualdiff_amd.%s: %d elements are more than one call takes" % (what, pred.numel()))
+    partials = torch.empty((need // 4,), dtype=torch.float32, device=pred.device)
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    grad = torch.empty_like(pred) if want_grad else None
+    _native.check(lib.dd_fgm_loss(_ptr(pred), _ptr(target), _ptr(heat), _ptr(grad), _ptr(loss), _ptr(partials), need, b * n,
+                                  c, h * w, FGM_LOSS_DTYPES[pred.dtype], _stream()), what)
+    return loss, grad
+
+
 MAP_MAX_LAYERS = 31                              # include/dualdiff_hip.h: DD_MAP_MAX_LAYERS; bit 31 of `used` is taken
 MAP_SIDES = {"right": 0, "below": 1}
 

@@ -20,8 +20,9 @@ synchronisation.
     bboxes_3d_data = pre(pay, [ex["gt_labels_3d"].data for ex in examples], trans, filter_corners=flt)
 
 The corners themselves come from the caller's box class (`reference_corners`): mmdet3d's corner order and yaw convention
-differ between its versions, so they are not restated here.  The training-time `bbox_add_ratio` / `bbox_drop_ratio` /
-`for_mask` paths, the projected `bboxes_coord` and `_preprocess_map_vec` stay with the caller.
+differ between its versions, so they are not restated here.  `for_mask` (dataset/utils.py:533-537) is this class with
+`use_3d_filter=False` on the re-centred corners, and `FgmMask` (fgm_mask.py) makes `heatmap_gt` of it.  The training-time
+`bbox_add_ratio` / `bbox_drop_ratio` paths, the projected `bboxes_coord` and `_preprocess_map_vec` stay with the caller.
 """
 import collections
 

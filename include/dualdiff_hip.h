@@ -1025,6 +1025,65 @@ int dd_bev_map_layers(const void* stat, int32_t static_bits, const float* corner
                       float* aux, int32_t* flags, dd_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * FGM loss mask (csrc/fgm_mask.hip, csrc/fgm_mask_core.h): `heatmap_gt` of the reference's collate_fn (magicdrive/dataset/
+ * utils.py:530-559), i.e. create_heatmap_gt(for_mask, lidar2image, metas, resolution) (magicdrive/networks/utils.py:26-39
+ * and :100-163: process_one_view_test, process_one_instance_test) followed by hd_crop (dataset/utils.py:348-353).
+ * Two launches: dd_fgm_box_records (one wave per box: its 96-byte record into the workspace, the area by a wave
+ * reduction) and dd_fgm_mask (pixel-major over the cropped output).  No atomics, nothing cleared, nothing allocated, no
+ * host synchronisation.
+ *   corners fp32 [views][m][points][3] (`for_mask["bboxes"]`, views = b * n), masks uint8 [views][m] (non-zero: the box
+ *   counts), lidar2image fp32 [views][4][4] (torch.bmm(camera_intrinsics, lidar2camera)).  All device memory.
+ *   Per box with mask set (utils.py:117-161): [x, y, z, 1] @ T.T in float64, every product and sum one IEEE operation,
+ *     summed k = 0..3; points with z <= 0 dropped; z clipped to [1e-5, 1e5]; x / z * sx and y / z * sy (sx = W / 1600, sy =
+ *     H / 900 as float64 quotients); truncated toward zero.  The polygon is the strict convex hull counter-clockwise in
+ *     (x, y) (scipy's ConvexHull(...).vertices) where that has >= 3 vertices, else the surviving points in corner order
+ *     (where ConvexHull raises); no point: nothing painted.  A pixel is painted where matplotlib's
+ *     Polygon(...).contains_point(p, radius=0) holds: the even-odd rule over the closed ring's edges v0 -> v1 with f = (vy >=
+ *     ty), an edge with f0 != f1 toggling iff ((v1y - ty) (v0x - v1x) >= (v1x - tx) (v0y - v1y)) == f1, in int64.  area =
+ *     the painted pixels of the UNCROPPED width x height grid; weight = float32(1.0 - area / (width * height)), float64.
+ *   out: fp32 [views][height_out][width_out]: per pixel the greatest weight among the boxes that paint it, 0 where none
+ *     does (torch.stack(res).max(0)); pixel (ox, oy) is grid pixel (ox + (width - width_out) / 2, oy + height - height_out),
+ *     hd_crop's window.  Every element is written.
+ *   flags: one int32, WRITTEN: the number of masked boxes that are unsupported — a projected x, y or z of a corner that
+ *     is not finite, or a surviving corner whose scaled coordinate is not finite or truncates beyond 2^25 in magnitude
+ *     (where the reference's float64 products of the crossing test stop being exact and its integer cast is undefined;
+ *     it takes z within ~1e-5 of the camera plane).  Such a box paints nothing.
+ *   workspace: at least dd_fgm_workspace_bytes(views * m) bytes, 16-byte aligned, contents don't care before; after the
+ *     call it holds the records (csrc/fgm_mask_core.h: ring, vertex count, flagged, weight, area, bounding box).
+ * DD_ERR_BAD_ARG, before any runtime call: a NULL workspace / out / flags, a NULL input with m > 0, views <= 0, m < 0,
+ * points outside [1, 8], width or height < 1, width * height > DD_FGM_MAX_PIXELS, an output larger than the grid or
+ * smaller than 1, width - width_out odd, a scale that is not finite, a misaligned array, workspace_bytes too small.
+ * views > 65535 or views * m > DD_FGM_MAX_BOXES: DD_ERR_UNSUPPORTED; dd_fgm_workspace_bytes returns -1 for such a total.
+ *
+ * dd_fgm_loss: the loss lines of runner/multiview_runner.py:501-507 — F.mse_loss(pred, target, reduction='none'), `loss *
+ * heatmap_gt[0].unsqueeze(2)`, the two .mean()s and their sum — as one read of each input:
+ *     loss[0] = sum((p - t)^2 * (1 + heat)) / N  in fp32,   N = views * channels * pixels,
+ * and, where grad is not NULL, grad = 2 (p - t) (1 + heat) / N in pred's type, in the same pass ((p - t), (1 + heat), its
+ * product with float32(2 / N), the product of the two: four fp32 roundings and the output cast).
+ *   pred, target, grad: [views][channels][pixels] of pred_dtype (DD_F16 / DD_BF16 / DD_F32); heat fp32 [views][pixels] or NULL
+ *   (the plain mean); loss: one fp32.
+ *   Reduction, fixed: groups = clamp(ceil(N / DD_FGM_LOSS_PER_GROUP), 1, DD_FGM_LOSS_MAX_GROUPS) workgroups of 256
+ *   lanes; lane l of group g sums elements (g * 256 + l) + k * groups * 256 in rising k, the 64 lanes of a wave by a
+ *   butterfly, the four waves in order; one workgroup then sums the partials the same way and divides by float32(N).  The
+ *   same inputs give the same bits.  workspace: dd_fgm_loss_workspace_bytes(N) bytes (the partials), 4-byte aligned.
+ * DD_ERR_BAD_ARG: a NULL pred / target / loss / workspace, a non-positive extent, an unknown pred_dtype, a misaligned array,
+ * workspace_bytes too small.  N > DD_FGM_LOSS_MAX_COUNT: DD_ERR_UNSUPPORTED (dd_fgm_loss_workspace_bytes: -1).
+ * ------------------------------------------------------------------------- */
+#define DD_FGM_MAX_BOXES (1 << 20)
+#define DD_FGM_MAX_PIXELS (1 << 20)
+#define DD_FGM_LOSS_PER_GROUP 1024
+#define DD_FGM_LOSS_MAX_GROUPS 1024
+#define DD_FGM_LOSS_MAX_COUNT 2147483647
+int64_t dd_fgm_workspace_bytes(int32_t total);
+int dd_fgm_mask(const float* corners, const uint8_t* masks, const float* lidar2image, int32_t views, int32_t m,
+                int32_t points, int32_t width, int32_t height, int32_t width_out, int32_t height_out, double sx, double sy,
+                void* workspace, int64_t workspace_bytes, float* out, int32_t* flags, dd_stream_t stream);
+int64_t dd_fgm_loss_workspace_bytes(int64_t count);
+int dd_fgm_loss(const void* pred, const void* target, const float* heat, void* grad, float* loss, void* workspace,
+                int64_t workspace_bytes, int64_t views, int32_t channels, int32_t pixels, int32_t pred_dtype,
+                dd_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * CLIP text encoder (csrc/clip.hip): the SD-v1.5 `text_encoder` (transformers.CLIPTextModel) that the reference calls at
  * runner/base_runner.py:119,511-514, runner/multiview_runner.py:145,427-428 (`text_encoder(ids)[0]`), through diffusers'
  * _encode_prompt at pipeline/pipeline_bev_controlnet.py:273 and at networks/bbox_embedder.py:133-145
