@@ -34,7 +34,9 @@ SOURCES = ["gemm23.hip", "gemm2_conv.hip", "attention.hip", "gemm1.hip", "conv3s
            "attn_probs.hip",
            # the heat-map sheets are made of the captured maps after the last step: behind everything, for the same reason.
            # No flag of its own below: its fp64 subtraction and division must stay IEEE-rounded (no fast-math, NaNs honoured)
-           "attn_heat.hip"]
+           "attn_heat.hip",
+           # the optimizer step belongs to training, no denoising step launches it: behind everything, for the same reason
+           "adamw.hip"]
 # per-source extra flags: the attention softmax lives on the MFMA results, so ask LLVM for the
 # VGPR-destination form of MFMA (gfx950 has a unified register file) instead of AGPR accumulators
 # that cost a v_accvgpr_read/write per touched element.
@@ -47,7 +49,10 @@ EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-hon
                "clip.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "attn_probs.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                # the BatchNorm + ReLU epilogue reads every accumulator: VGPR results, as for the GEMM kernels
-               "conv2d.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+               "conv2d.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               # the update is stated as single IEEE fp32 operations (csrc/adamw_core.h): no fused multiply-adds, division
+               # and square root correctly rounded
+               "adamw.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]}
 ARCH = "gfx950"
 
 

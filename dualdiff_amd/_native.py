@@ -160,6 +160,10 @@ SIGNATURES = {
     "dd_fgm_loss_workspace_bytes": (c_int64, [c_int64]),
     "dd_fgm_loss": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32,
                               c_int32, c_int32, c_void_p]),
+    "dd_adamw_workspace_bytes": (c_int64, [c_int64]),
+    "dd_adamw_step": (c_int32, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                                c_double, c_double, c_double, c_double, c_double, c_int32, c_void_p, c_int64, c_int32,
+                                c_void_p]),
     "dd_fourier_embed": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, POINTER(c_float), c_int32, c_int32,
                                    c_int32, c_int32, c_void_p]),
     "dd_conv3x3_small_cout": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,

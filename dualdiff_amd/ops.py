@@ -1171,6 +1171,160 @@ def fgm_loss(pred, target, heat=None, want_grad=False):
     return loss, grad
 
 
+ADAMW_CHUNK = 8192                               # include/dualdiff_hip.h: DD_ADAMW_CHUNK
+ADAMW_ROW_WORDS, ADAMW_STATE_BYTES = 6, 96       # dd_adamw_row as int64 words (p, g, m, v, shadow, numel); dd_adamw_state
+ADAMW_STATE_FIELDS = {                           # name -> (byte offset, type) of dd_adamw_state
+    "step": (0, torch.int64), "beta1_pow": (8, torch.float64), "beta2_pow": (16, torch.float64),
+    "grad_norm": (24, torch.float32), "clip_coef": (28, torch.float32), "found_inf": (32, torch.int32),
+    "skipped": (40, torch.int64), "lr": (48, torch.float32), "decay": (52, torch.float32), "w1": (56, torch.float32),
+    "b2": (60, torch.float32), "w2": (64, torch.float32), "step_size": (68, torch.float32), "bc2_sqrt": (72, torch.float32),
+    "eps": (76, torch.float32), "inv_scale": (80, torch.float32)}
+ADAMW_SHADOW_DTYPES = {torch.float16: DD_F16, torch.bfloat16: DD_BF16}
+ADAMW_ALL = 7                                    # DD_ADAMW_ALL: the three launches of a step
+
+
+def adamw_chunk():
+    """the elements of one chunk of dd_adamw_step's table (include/dualdiff_hip.h: DD_ADAMW_CHUNK)"""
+    return ADAMW_CHUNK
+
+
+def adamw_chunks(numels):
+    """The chunk list of a table whose rows have these element counts -> int32 (n_chunks, 2) on the host: (row, chunk of
+    the row), row-major.  A row with no element has no chunk."""
+    per_row = [(int(n) + ADAMW_CHUNK - 1) // ADAMW_CHUNK for n in numels]
+    if any(int(n) < 0 for n in numels) or sum(per_row) > 2 ** 31 - 1:
+        raise ValueError("adamw_chunks: element counts must be non-negative and give fewer than 2^31 chunks")
+    if not per_row:
+        return torch.empty((0, 2), dtype=torch.int32)
+    rows =torch.repeat_interleave(torch.arange(len(per_row), dtype=torch.int32), torch.tensor(per_row, dtype=torch.int64))
+    first = torch.cumsum(torch.tensor([0] + per_row[:-1], dtype=torch.int64), 0)
+    within = torch.arange(rows.numel(), dtype=torch.int64) - torch.repeat_interleave(first, torch.tensor(per_row, dtype=torch.int64))
+    return torch.stack([rows, within.to(torch.int32)], 1).contiguous()
+
+
+def adamw_table(rows):
+    """The descriptor table of dd_adamw_step for rows = [(p, g, m, v, shadow), ...] -> int64 (n, 6) on the host, to be
+    copied to the device.  p, m, v: fp32; g: fp32 or None (the row is left alone); shadow: fp16 / bf16 or None — all of
+    p's shape, contiguous, on p's device, which is one GPU for the whole table.  Checked here, on the host, before any
+    launch; an error names the offending row.  -> (table, the shadows' dtype or None)."""
+    what = "adamw_table"
+    words, shadow_dtype, device = [], None, None
+    for i, row in enumerate(rows):
+        if len(row) != 5:
+            raise ValueError("%s: row %d is not (p, g, m, v, shadow)" % (what, i))
+        p, g, m, v, shadow = row
+        for name, t, optional in (("p", p, False), ("g", g, True), ("m", m, False), ("v", v, False)):
+            if t is None and optional:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+                raise TypeError("%s: row %d: %s must be an fp32 tensor, got %s"
+                                % (what, i, name, t.dtype if isinstance(t, torch.Tensor) else type(t).__name__))
+        if shadow is not None:
+            if not isinstance(shadow, torch.Tensor) or shadow.dtype not in ADAMW_SHADOW_DTYPES:
+                raise TypeError("%s: row %d: the shadow must be an fp16 or bf16 tensor, got %s"
+                                % (what, i, shadow.dtype if isinstance(shadow, torch.Tensor) else type(shadow).__name__))
+            if shadow_dtype is not None and shadow.dtype != shadow_dtype:
+                raise TypeError("%s: row %d: the shadow is %s, the rows before have %s shadows (one type per table)"
+                                % (what, i, shadow.dtype, shadow_dtype))
+            shadow_dtype = shadow.dtype
+        for name, t in (("g", g), ("m", m), ("v", v), ("shadow", shadow)):
+            if t is None:
+                continue
+            if t.shape != p.shape:
+                raise ValueError("%s: row %d: %s has shape %s, p has %s" % (what, i, name, tuple(t.shape), tuple(p.shape)))
+            if t.device != p.device:
+                raise ValueError("%s: row %d: %s is on %s, p is on %s" % (what, i, name, t.device, p.device))
+        for name, t in (("p", p), ("g", g), ("m", m), ("v", v), ("shadow", shadow)):
+            if t is not None and not t.is_contiguous():
+                raise ValueError("%s: row %d: %s is not contiguous" % (what, i, name))
+        if device is not None and p.device != device:
+            raise ValueError("%s: row %d is on %s, the rows before are on %s" % (what, i, p.device, device))
+        device = p.device
+        words.append([p.data_ptr(), 0 if g is None else g.data_ptr(), m.data_ptr(), v.data_ptr(),
+                      0 if shadow is None else shadow.data_ptr(), p.numel()])
+    if device is not None and device.type != "cuda":                # after the rows' own faults, which need no GPU to be found
+        raise RuntimeError("%s: dualdiff_amd ops run on the GPU only (the rows are on %s); there is no CPU fallback"
+                           % (what, device))
+    return torch.tensor(words, dtype=torch.int64).reshape(len(words), ADAMW_ROW_WORDS), shadow_dtype
+
+
+def adamw_state(step=0, betas=(0.9, 0.999), skipped=0):
+    """the bytes of a dd_adamw_state after `step` taken steps, as a uint8 (96,) tensor on the host: the running products
+    start from Python's beta ** step, everything else is zero"""
+    import struct
+    block = struct.pack("<qddffiiq", int(step), float(betas[0]) ** int(step), float(betas[1]) ** int(step), 0.0, 0.0, 0, 0,
+                        int(skipped))
+    return torch.frombuffer(bytearray(block.ljust(ADAMW_STATE_BYTES, b"\0")), dtype=torch.uint8).clone()
+
+
+def adamw_state_field(state, name):
+    """a one-element view of a field of the state block (device or host), of the field's own type"""
+    at, dtype = ADAMW_STATE_FIELDS[name]
+    return state[at:at + torch.empty((), dtype=dtype).element_size()].view(dtype)
+
+
+def adamw_workspace_bytes(n_chunks):
+    n = _native.load().dd_adamw_workspace_bytes(int(n_chunks))
+    if n < 0:
+        raise _native.Unsupported("dualdiff_amd.adamw_step: %d chunks are more than one call takes" % n_chunks)
+    return n
+
+
+def adamw_step(table, chunks, state, lr_table, *, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
+               grad_scale=None, found_inf=None, shadow_dtype=torch.float16, workspace=None, written=(), launches=ADAMW_ALL):
+    """One optimizer step over a descriptor table in three launches — GradScaler's unscale and non-finite search,
+    clip_grad_norm_, torch.optim.AdamW's update, the 16-bit shadows — with nothing read back (include/dualdiff_hip.h:
+    dd_adamw_step; runner/multiview_runner.py:512-521).  table int64 (n, 6) (adamw_table), chunks int32 (n_chunks, 2)
+    (adamw_chunks), state uint8 (96,) (adamw_state), lr_table fp32 (len >= 1,), grad_scale / found_inf one fp32 each or None
+    — contiguous tensors of one GPU.  written: a list of the tensors of the caller's that the table points to and a taken
+    step rewrites (every p, m, v and shadow of a row with a gradient; no None, no inference tensor); each counts a version.  workspace: a uint8 device tensor
+    of at least adamw_workspace_bytes(n_chunks) bytes (default: a new one).  launches: ADAMW_ALL, or a subset of the three
+    for timing."""
+    what = "adamw_step"
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != ADAMW_ROW_WORDS or not table.is_contiguous():
+        raise ValueError("%s takes a contiguous int64 table (n, %d), got %s %s"
+                         % (what, ADAMW_ROW_WORDS, table.dtype, tuple(table.shape)))
+    if chunks.dtype != torch.int32 or chunks.dim() != 2 or chunks.shape[1] != 2 or not chunks.is_contiguous():
+        raise ValueError("%s takes contiguous int32 chunks (n_chunks, 2), got %s %s" % (what, chunks.dtype, tuple(chunks.shape)))
+    if state.dtype != torch.uint8 or state.numel() < ADAMW_STATE_BYTES or not state.is_contiguous():
+        raise ValueError("%s takes a contiguous uint8 state block of %d bytes" % (what, ADAMW_STATE_BYTES))
+    if lr_table.dtype != torch.float32 or lr_table.dim() != 1 or lr_table.numel() < 1 or not lr_table.is_contiguous():
+        raise ValueError("%s takes a contiguous 1-D fp32 lr_table with at least one entry, got %s %s"
+                         % (what, lr_table.dtype, tuple(lr_table.shape)))
+    for name, t in (("grad_scale", grad_scale), ("found_inf", found_inf)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != 1):
+            raise ValueError("%s: %s must be one fp32 value, got %s %s" % (what, name, t.dtype, tuple(t.shape)))
+    if shadow_dtype not in ADAMW_SHADOW_DTYPES:
+        raise TypeError("%s: shadows are fp16 or bf16, got %s" % (what, shadow_dtype))
+    beta1, beta2 = (float(b) for b in betas)
+    if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0) or not eps >= 0.0 or not weight_decay >= 0.0:
+        raise ValueError("%s: betas in [0, 1), eps >= 0, weight_decay >= 0, got %r, %r, %r" % (what, betas, eps, weight_decay))
+    if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+        raise ValueError("%s: max_grad_norm must be None or >= 0, got %r" % (what, max_grad_norm))
+    if not 1 <= int(launches) <= ADAMW_ALL:
+        raise ValueError("%s: launches is a mask in [1, %d], got %r" % (what, ADAMW_ALL, launches))
+    ins = (table, chunks, state, lr_table, grad_scale, found_inf)
+    _need_gpu(*ins)
+    if any(t is not None and t.device != table.device for t in ins):
+        raise ValueError("%s takes tensors of one device" % what)
+    need = adamw_workspace_bytes(chunks.shape[0])
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=table.device)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous() \
+            or workspace.device != table.device:
+        raise ValueError("%s: the workspace must be a contiguous uint8 tensor of at least %d bytes on %s"
+                         % (what, need, table.device))
+    _written(state, workspace)
+    if written:                        # _written's count, in one call for the hundreds of tensors of a table (1 ms otherwise)
+        torch.autograd.graph.increment_version(written)
+    lib = _native.load()
+    _native.check(lib.dd_adamw_step(_ptr(table), table.shape[0], _ptr(chunks), chunks.shape[0], _ptr(state), _ptr(lr_table),
+                                    lr_table.numel(), _ptr(grad_scale), _ptr(found_inf), beta1, beta2, float(eps),
+                                    float(weight_decay), -1.0 if max_grad_norm is None else float(max_grad_norm),
+                                    ADAMW_SHADOW_DTYPES[shadow_dtype], _ptr(workspace), workspace.numel(), int(launches),
+                                    _stream()), what)
+
+
 MAP_MAX_LAYERS = 31                              # include/dualdiff_hip.h: DD_MAP_MAX_LAYERS; bit 31 of `used` is taken
 MAP_SIDES = {"right": 0, "below": 1}
 

@@ -1084,6 +1084,69 @@ int dd_fgm_loss(const void* pred, const void* target, const float* heat, void* g
                 dd_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Fused optimizer step (csrc/adamw.hip, csrc/adamw_core.h): the last three lines of the reference's training step
+ * (runner/multiview_runner.py:512-521) — accelerator.clip_grad_norm_, torch.optim.AdamW.step() under a GradScaler
+ * (mixed_precision: fp16) and the scheduler's step — in three launches with nothing read back: the step count, the
+ * learning rate and the skip decision live in device memory, so a step can be captured into a graph.
+ *   rows: n_rows descriptors in device memory, one per parameter tensor.  p, g, m, v: fp32, 4-byte aligned; g NULL: the
+ *     row is left entirely alone (a parameter without a gradient); shadow: NULL, or numel elements of shadow_dtype (DD_F16 /
+ *     DD_BF16), 2-byte aligned, rewritten with the new p; numel >= 0.
+ *   chunks: n_chunks pairs (row, chunk of the row) of int32 in device memory: chunk c of a row covers its elements
+ *     [c * DD_ADAMW_CHUNK, min((c + 1) * DD_ADAMW_CHUNK, numel)).  Every element of every row with numel > 0 is covered
+ *     once; a pair that names no row or lies past a row's end is skipped.
+ *   state: the block below, device memory, 8-byte aligned.  lr_table: lr_len >= 1 fp32 in device memory, indexed by the
+ *     number of steps taken before this one, the last entry for every step past the end.
+ *   grad_scale: NULL (1), or one fp32 in device memory; inv_scale = fp32(1 / float64(grad_scale)).  found_inf_in: NULL,
+ *     or one fp32 in device memory whose non-zero value skips the step (GradScaler's `optimizer.found_inf`).
+ *   max_norm < 0: no clipping (clip_coef = 1).
+ * Launch 1 (a workgroup per chunk): gu = fl32(g * inv_scale) per element; the workgroup's float64 sum of gu^2 (an fp32
+ *   square is exact in float64) in a fixed order — lane l sums elements 4 (256 i + l) + c of the chunk in rising i, c; the
+ *   64 lanes of a wave by a butterfly; waves 0..3 in order — into partials[chunk], and whether a gu was not finite.
+ * Launch 2 (one workgroup): the partials summed the same way (lane l: partials l + 256 i), then, in float64, each result
+ *   rounded to fp32 once: grad_norm = sqrt(sum), clip_coef = min(max_norm / (grad_norm + 1e-6), 1)
+ *   (torch.nn.utils.clip_grad_norm_); found_inf = a non-finite gu or a non-zero found_inf_in.  Skipped step: skipped += 1 and
+ *   nothing else.  Taken step: step += 1, beta1_pow *= beta1, beta2_pow *= beta2, lr = lr_table[min(step - 1, lr_len - 1)],
+ *   decay = 1 - lr wd, w1 = 1 - beta1, b2 = beta2, w2 = 1 - beta2, step_size = lr / (1 - beta1_pow),
+ *   bc2_sqrt = sqrt(1 - beta2_pow), eps.
+ * Launch 3 (a workgroup per chunk; returns at once when found_inf is set): csrc/adamw_core.h's update, every operation
+ *   one IEEE fp32 operation, then the shadow.  16-byte accesses where p, g, m and v of the row share their offset in a
+ *   16-byte line (a scalar head of up to three elements and a scalar tail), dword accesses otherwise.  The gradients
+ *   are not rewritten: they keep their scaled, unclipped values.
+ * The same inputs give the same bits, wherever the tensors lie.  launches: bit 0 / 1 / 2 = issue launch 1 / 2 / 3
+ * (DD_ADAMW_ALL for a step; single launches are for timing).  workspace: dd_adamw_workspace_bytes(n_chunks) bytes,
+ * 8-byte aligned: the partials and the non-finite marks.
+ * DD_ERR_BAD_ARG, before any runtime call: a NULL rows / chunks with n_rows / n_chunks > 0, a NULL state / lr_table /
+ * workspace, negative counts, lr_len < 1, betas outside [0, 1), eps or weight_decay negative or not finite, a NaN max_norm,
+ * an unknown shadow_dtype, launches outside [1, 7], a misaligned pointer, workspace_bytes too small.
+ * ------------------------------------------------------------------------- */
+#ifndef DD_ADAMW_CHUNK                            /* another size only in an A/B build (tools/adamw_timing.py) */
+#define DD_ADAMW_CHUNK 8192
+#endif
+#define DD_ADAMW_ALL 7
+typedef struct dd_adamw_row {
+  void* p;
+  const void* g;
+  void* m;
+  void* v;
+  void* shadow;
+  int64_t numel;
+} dd_adamw_row;                                   /* 48 bytes */
+typedef struct dd_adamw_state {
+  int64_t step;                                   /* steps taken */
+  double beta1_pow, beta2_pow;                    /* beta^step, advanced by one multiplication per taken step */
+  float grad_norm, clip_coef;                     /* of the last call, taken or not */
+  int32_t found_inf, reserved0;                   /* 1: the last call was skipped */
+  int64_t skipped;                                /* calls skipped */
+  float lr, decay, w1, b2, w2, step_size, bc2_sqrt, eps;   /* of the last taken step */
+  float inv_scale, reserved1[3];                  /* of the last call */
+} dd_adamw_state;                                 /* 96 bytes */
+int64_t dd_adamw_workspace_bytes(int64_t n_chunks);
+int dd_adamw_step(const dd_adamw_row* rows, int32_t n_rows, const int32_t* chunks, int64_t n_chunks,
+                  dd_adamw_state* state, const float* lr_table, int32_t lr_len, const float* grad_scale,
+                  const float* found_inf_in, double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                  int32_t shadow_dtype, void* workspace, int64_t workspace_bytes, int32_t launches, dd_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * CLIP text encoder (csrc/clip.hip): the SD-v1.5 `text_encoder` (transformers.CLIPTextModel) that the reference calls at
  * runner/base_runner.py:119,511-514, runner/multiview_runner.py:145,427-428 (`text_encoder(ids)[0]`), through diffusers'
  * _encode_prompt at pipeline/pipeline_bev_controlnet.py:273 and at networks/bbox_embedder.py:133-145
